@@ -1,6 +1,6 @@
 """bench.py — headline benchmark of the Factorizer hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +13,9 @@ One JSON line is printed by rank 0.  `roofline` describes the dominant native ke
 timed region (HIP events on the launch stream, algorithmic bytes of SURVEY.md §8d);
 `cpu_baseline` is the CPU oracle (oracle/cpu_ref.py, a port of the reference's CPU path) timed
 on this host on a bounded sample (rank 0, N=1 only).
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as float32 .npy files, so that two builds
+run with the same arguments can be compared output for output: see `dump_outputs`.
 """
 from __future__ import annotations
 
@@ -141,6 +144,29 @@ MODEL_KW = dict(in_channels=4, out_channels=3, spatial_size=(128, 128, 128),
                 reshape=(ft.SWMatricize, {"head_dim": 8, "patch_size": 8}), act=nn.ReLU,
                 factorize=ft.NMF, rank=1, num_iters=5, init="uniform", solver="hals", mlp_ratio=2,
                 dropout=0.1)
+
+
+DUMP_LOGITS_SAMPLE = 1 << 21   # logits kept by --dump-outputs: 8 MB of the 50 MB a batch of 2 produces
+
+
+def dump_outputs(path, model, loss, logits):
+    """Write the outputs of the last timed step to `path` as float32 .npy files, 55 MB in all:
+    loss.npy (1 value); logits.npy, the model output at DUMP_LOGITS_SAMPLE positions drawn by a CPU generator seeded
+    with 0 and sorted (the same positions for every run of the same shape; all of it when smaller); params.npy and
+    grads.npy, every trainable parameter after the optimizer step and the gradient that step applied, flattened and
+    concatenated in model.parameters() order."""
+    import numpy as np
+    flat = logits.detach().reshape(-1)
+    if flat.numel() > DUMP_LOGITS_SAMPLE:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_LOGITS_SAMPLE].sort().values
+        flat = flat[idx.to(flat.device)]
+    params = [p for p in model.parameters() if p.requires_grad]
+    arrays = {"loss": loss.detach().reshape(1), "logits": flat,
+              "params": torch.cat([p.detach().reshape(-1) for p in params]),
+              "grads": torch.cat([p.grad.detach().reshape(-1) for p in params])}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
 
 
 def cpu_baseline_sample(batch=2, timed=3, all_threads=False):
@@ -438,7 +464,12 @@ def main():
     ap.add_argument("--no-late-join", action="store_true",
                     help="await the side-stream weight gradients at the end of every block backward "
                          "(factorizer_amd/pointwise.py:_LateJoin)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the loss, a fixed sample of the logits, the parameters and the gradients "
+                         "of the last timed step to DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -490,14 +521,15 @@ def main():
     import contextlib
     amp = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if args.dtype == "bf16" else contextlib.nullcontext
 
-    def step():
+    def step(keep_logits=False):
         sync.zero_grad()
         with amp():
-            loss = ft.dice_ce_loss(model(x), target)   # the recipe's DiceCELoss(sigmoid, squared_pred), train.yaml:67-70
+            logits = model(x)
+            loss = ft.dice_ce_loss(logits, target)   # the recipe's DiceCELoss(sigmoid, squared_pred), train.yaml:67-70
         loss.backward()
         scale = sync.finish(average=False)          # SUM stays in the buffer; 1/world is applied by the optimizer kernel
         opt.step(grad_scale=scale)
-        return loss
+        return loss, (logits if keep_logits else None)
 
     # Warm-up steps run with EVERY native launch bracketed by HIP events: that pass yields the per-kernel
     # table and names the dominant kernel.  In the timed region only that kernel is bracketed (two
@@ -527,8 +559,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        # only the last step's logits are held past the step, and only for --dump-outputs
+        loss, logits = step(keep_logits=args.dump_outputs is not None and i == args.steps - 1)
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -539,6 +572,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(loss).item(), "loss is not finite"
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, model, loss, logits)
+    del logits
 
     copy_gbs = None
     if rank == 0:

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("FZ_LIB_PATH") or os.path.join(_HERE, "libfactorizer_h
 
 FZ_OK = 0
 FZ_E_UNSUPPORTED = -2
-ABI_VERSION = 6   # include/factorizer_hip.h: FZ_ABI_VERSION this binding's argument lists / descriptor layouts are written against
+ABI_VERSION = 7   # include/factorizer_hip.h: FZ_ABI_VERSION this binding's argument lists / descriptor layouts are written against
 SOLVER_ID = {"mu": 0, "hals": 1}
 STORE_F32, STORE_BF16 = 0, 1   # include/factorizer_hip.h: FZ_STORE_*
 PRODUCTS_DEFAULT, PRODUCTS_SPLIT_BF16, PRODUCTS_FP32_MFMA = 0, 1, 2   # FZ_PRODUCTS_*: the `products` field of the descriptors
@@ -191,6 +191,11 @@ class MlpDesc(_c.Structure):
                 ("post_w", _vp), ("post_b", _vp), ("post_out", _vp), ("post_m", _i)]
 
 
+class MlpDropout(_c.Structure):
+    """fz_mlp_dropout (include/factorizer_hip.h): the block's dropout planes and scales for fz_mlp_chain_drop"""
+    _fields_ = [("m0", _vp), ("m1", _vp), ("m2", _vp), ("s0", _f), ("s1", _f), ("s2", _f)]
+
+
 class BlockPrologue(_c.Structure):
     """fz_block_prologue (include/factorizer_hip.h)"""
     _fields_ = [("ln_g", _vp), ("ln_b", _vp), ("ln_eps", _f), ("w", _vp), ("t", _vp), ("stats", _vp)]
@@ -199,7 +204,7 @@ class BlockPrologue(_c.Structure):
 class GemmDwDesc(_c.Structure):
     _fields_ = [("g", _vp), ("q", _vp), ("w", _vp), ("ln", _i), ("stats", _vp), ("ln_g", _vp), ("ln_b", _vp), ("gadd", _vp),
                 ("y", _vp), ("gln", _vp), ("wpart", _vp), ("gw", _vp), ("gb", _vp), ("B", _i), ("C", _i), ("V", _i64),
-                ("act_dtype", _i), ("ldgw", _i), ("ldw", _i)]
+                ("act_dtype", _i), ("ldgw", _i), ("ldw", _i), ("drop_m", _vp), ("drop_s", _f)]
 
 
 class WgradDesc(_c.Structure):
@@ -229,6 +234,8 @@ _SIGS.update({
     "fz_nmf_pcf_bwd_prefers_separate": ([_i] * 4, _i),
     "fz_act_add": ([_vp, _vp, _i64, _i, _vp], _i),
     "fz_mlp_pre_supported": ([_i, _i, _i64, _i], _i),
+    "fz_mlp_drop_supported": ([_i, _i, _i64, _i], _i),
+    "fz_mlp_chain_drop": ([_c.POINTER(MlpDesc), _c.POINTER(MlpDropout), _vp], _i),
     "fz_conv3_prologue_supported": ([_i] * 4, _i),
     "fz_conv3_fwd2": ([_vp] * 4 + [_i] * 8 + [_c.POINTER(BlockPrologue), _vp], _i),
     "fz_upcat2": ([_vp, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_c.POINTER(BlockPrologue), _vp], _i),
@@ -280,4 +287,8 @@ _SIGS.update({
     "fz_ln_bwd": ([_vp] * 8 + [_i, _i, _i64, _i, _vp], _i),
     "fz_ln_bwd_workspace_bytes": ([_i], _i64),
     "fz_ln_bwd_workspace_bytes2": ([_i, _i, _i64], _i64),
+    "fz_dropout_bits_words": ([_i, _i, _i64], _i64),
+    "fz_dropout_keep_bits": ([_vp, _i, _i, _i, _i64, _f, _vp, _vp], _i),
+    "fz_dropout_apply": ([_i, _vp, _f, _vp, _vp, _vp, _i, _i, _i64, _i, _vp], _i),
 })
+DROP_RES, DROP_GELU, DROP_GELU_BWD = 0, 1, 2   # include/factorizer_hip.h: FZ_DROP_*

@@ -74,8 +74,8 @@ class FactorizerBlock(nn.Module):
 
     def _fusable(self, x) -> bool:
         """Standard Swin block on a device tensor (fp32, or bf16 activations with fp32 parameters): LayerNorm / ReLU / exact GELU, no live
-        dropout — then LayerNorm, bias, ReLU, GELU and both residual adds are fused into the GEMM
-        kernels (csrc/gemm.hip) instead of running as separate full-tensor passes."""
+        dropout or live torch.nn.Dropout with p < 1 — then LayerNorm, bias, ReLU, GELU and both residual adds are fused into the GEMM
+        kernels (csrc/gemm.hip) instead of running as separate full-tensor passes; live dropout only on the one-node path."""
         f, m = self.fact, self.mlp
         if not (x.is_cuda and x.numel() and x.dtype in (torch.float32, torch.bfloat16) and PW._vox(x) % 4 == 0
                 and x.shape[1] % 2 == 0):
@@ -92,8 +92,16 @@ class FactorizerBlock(nn.Module):
         if not (len(blk) == 5 and isinstance(blk[1], nn.GELU) and blk[1].approximate == "none"
                 and blk[0].linear.weight.shape[0] % 2 == 0):
             return False
-        live = self.training and (f.dropout.p > 0 or blk[2].p > 0 or blk[4].p > 0)
-        return not live
+        drops = (f.dropout, blk[2], blk[4])
+        if self.training and any(d.p > 0 for d in drops):
+            # live dropout runs inside the one-node path (csrc/dropout.hip): exactly torch.nn.Dropout at every site, 0 <= p < 1
+            return all(type(d) is nn.Dropout and 0 <= d.p < 1 for d in drops)
+        return True
+
+    def _dropout_ps(self):
+        """(p0, p1, p2) of the three dropout sites (fact.dropout, mlp.block[2], mlp.block[4]) when any is live, else None"""
+        ps = (float(self.fact.dropout.p), float(self.mlp.block[2].p), float(self.mlp.block[4].p))
+        return ps if self.training and any(p > 0 for p in ps) else None
 
     def _modular_native_cfg(self, x) -> bool:
         """matricize / NMF / inverse all covered by the native modular kernels (any patch size)."""
@@ -142,21 +150,25 @@ class FactorizerBlock(nn.Module):
             core = self._core_cfg()
             mf = f.factorize
             nat = core is not None or self._modular_native_cfg(x)
-            if nat and f.in_proj.linear.bias is None and blk[0].linear.bias is not None \
-                    and blk[3].linear.bias is not None and f.out_proj.linear.bias is not None:
+            drop = self._dropout_ps()
+            one_node = nat and f.in_proj.linear.bias is None and blk[0].linear.bias is not None \
+                and blk[3].linear.bias is not None and f.out_proj.linear.bias is not None
+            if one_node:
                 if core is not None:
                     G, sid = core
                 else:
                     G, sid = min(max(mf.num_grad_steps, 0), mf.num_iters), mf.solver.native_id
                 cfg = dict(geo=f.reshape.geometry, T=mf.num_iters, G=G, solver=sid, nmf_eps=mf.solver.eps,
                            eps1=n1.eps, eps2=n2.eps, core=core is not None)
+                if drop is not None:
+                    cfg["drop"] = drop   # the three sites inside the node (pointwise._block_dropout_fwd)
                 args = (x, n1.weight, n1.bias, f.in_proj.linear.weight, mf.init.u0, mf.init.v0,
                         f.out_proj.linear.weight, f.out_proj.linear.bias, n2.weight, n2.bias,
                         blk[0].linear.weight, blk[0].linear.bias, blk[3].linear.weight, blk[3].linear.bias, cfg)
                 pre = PW.BlockPrologue.take(x) if core is not None else None   # t, statistics already formed by x's producer
                 t_pre, st_pre = pre if pre is not None else (None, None)
                 slot = PW.head_fusion_slot()
-                if slot is not None and slot.block is self and core is not None:
+                if slot is not None and slot.block is self and core is not None and drop is None:
                     # this block's output feeds ONLY the network's head (ushape.UNet.forward): the head runs inside the
                     # block's last launch, HeadOfBlockFn carries its gradient
                     hw, hb = slot.head_params
@@ -166,15 +178,21 @@ class FactorizerBlock(nn.Module):
                         slot.logits = PW.HeadOfBlockFn.apply(y, hw, hb, raw)
                         return y
                 return PW.FactorizerBlockFn.apply(*args, None, None, t_pre, st_pre)
-            # per-layer fused path (composed NMF, unusual bias layout, ...)
-            t = PW.ln_linear(x, n1.weight, n1.bias, n1.eps, f.in_proj.linear.weight, f.in_proj.linear.bias, "relu")
-            a = f.reshape.inverse_forward(f.factorize(f.reshape(t)))  # ReLU already applied (commutes)
-            x = PW.act_linear_res(a, f.out_proj.linear.weight, f.out_proj.linear.bias, x, "none")
-            z = PW.ln_linear(x, n2.weight, n2.bias, n2.eps, blk[0].linear.weight, blk[0].linear.bias, "none")
-            return PW.act_linear_res(z, blk[3].linear.weight, blk[3].linear.bias, x, "gelu")
+            if drop is None:
+                return self._per_layer(x)
         x = x + self.fact(self.norm1(x))
         x = x + self.mlp(self.norm2(x))
         return x
+
+    def _per_layer(self, x):
+        """per-layer fused path (composed NMF, unusual bias layout, ...): no dropout site is live here"""
+        f, blk = self.fact, self.mlp.block
+        n1, n2 = self.norm1.norm, self.norm2.norm
+        t = PW.ln_linear(x, n1.weight, n1.bias, n1.eps, f.in_proj.linear.weight, f.in_proj.linear.bias, "relu")
+        a = f.reshape.inverse_forward(f.factorize(f.reshape(t)))  # ReLU already applied (commutes)
+        x = PW.act_linear_res(a, f.out_proj.linear.weight, f.out_proj.linear.bias, x, "none")
+        z = PW.ln_linear(x, n2.weight, n2.bias, n2.eps, blk[0].linear.weight, blk[0].linear.bias, "none")
+        return PW.act_linear_res(z, blk[3].linear.weight, blk[3].linear.bias, x, "gelu")
 
 
 class FactorizerStage(nn.Module):

@@ -470,6 +470,27 @@ __global__ __launch_bounds__(256, 2) void gemm_p32_kernel(GemmArgsT<AT> p, unsig
   }
 }
 
+// Block dropout inside the fused launches (csrc/dropout.hip has the contract): keep-bit planes (B, ch, nw) of sites 0..2, bit v & 31
+// of word v >> 5 of row (b, ch); a null plane keeps everything.  The dropout forms are separate instantiations of the kernels with
+// ONE trailing DropArgs argument (DROP = a non-empty parameter pack): the p = 0 instantiations keep their argument list and code.
+struct DropArgs {
+  const uint32_t* m[3];   // site 0: out_proj output, site 1: gelu(z1), site 2: fc2 output (C = 32 / hidden 64 / C = 32 channels)
+  float s[3];             // 1 / (1 - p)
+  int64_t nw;             // words per row: ceil(V / 32)
+};
+// the keep bits of voxels v, v + 1, ... (v even, NACC <= 2: one word) of row `row` of sample b in a plane of `ch` rows, shifted
+// down to bit 0; all ones when the site is not live
+__device__ __forceinline__ uint32_t drop_bits(const DropArgs& d, int site, int b, int ch, int row, int64_t v) {
+  const uint32_t* m = d.m[site];
+  if (m == nullptr) return ~0u;
+  return m[((int64_t)b * ch + row) * d.nw + (v >> 5)] >> (v & 31);
+}
+__device__ __forceinline__ DropArgs drop_of() { return DropArgs{}; }
+__device__ __forceinline__ DropArgs drop_of(const DropArgs& d) { return d; }
+__device__ __forceinline__ float drop_f(const DropArgs& d, int site, uint32_t bits, int q, float v) {
+  return ((bits >> q) & 1u) ? v * d.s[site] : 0.f;
+}
+
 // =================================================================================================
 // Kernel C — two chained GEMMs for the C = 32 MLP (layers/mlp.py:54-63 behind the second pre-norm
 // residual, factorizer.py:76): the 64-row hidden tensor is produced in the accumulators of GEMM 1,
@@ -526,8 +547,11 @@ __device__ __forceinline__ void chain_stagger(int stagger) {
 // kernel's time with nothing running beside them — a bf16 MFMA for a quarter of its own.
 // (Six-wave workgroups — 73 KB, two per CU, three waves per SIMD again — were tried and are slower than these four-wave ones at two
 // waves per SIMD: 1.06 against 0.97 ms per step for the two launches, fp32 form 1.09; profiles/r04_chain_fwd_bx_ab.log.)
-template <bool BWD, int NACC, int HB, typename AT = float, bool BX = false, bool PRE = false>
-__global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2) void gemm_chain_kernel(GemmArgsT<AT> p, ChainArgsT<AT> c, int ntiles) {
+template <bool BWD, int NACC, int HB, typename AT = float, bool BX = false, bool PRE = false, typename... DropX>
+__global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2) void gemm_chain_kernel(GemmArgsT<AT> p, ChainArgsT<AT> c, int ntiles, DropX... dx) {
+  constexpr bool DROP = sizeof...(DropX) > 0;   // the block-dropout form: one trailing DropArgs (the p = 0 kernels have no such argument)
+  const DropArgs dr = drop_of(dx...);
+  static_assert(!DROP || (PRE && !BWD && NACC == 2), "dropout: the forward chain with the out-projection in front");
   constexpr int NW = 4;
   constexpr int HID = 32 * HB, N1 = BX ? 1536 * HB : 16 * HB * 64;  // hidden rows; floats of each staged weight block
   static_assert(!BX || (!BWD && NACC == 2), "the split-bf16 form is the forward chain");
@@ -695,9 +719,13 @@ __global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2)
         const int rbase = (r & 3) + 8 * (r >> 2);
         const int row = rbase + 4 * h;
         const float add = tB0[row];
+        uint32_t dk = 0;
+        if constexpr (DROP) dk = drop_bits(dr, 0, b, 32, row, nc);
 #pragma unroll
         for (int q = 0; q < NACC; ++q) {
-          float v = acc0[q][r] + add + xr[PRE ? r : 0][q];
+          float v;
+          if constexpr (DROP) v = drop_f(dr, 0, dk, q, acc0[q][r] + add) + xr[PRE ? r : 0][q];
+          else v = acc0[q][r] + add + xr[PRE ? r : 0][q];
           // bf16 storage: everything downstream (LayerNorm, the chain's residual, the backward) sees the STORED x1, as in the
           // two-launch form where the chain reads it back
           if constexpr (sizeof(AT) == 2) v = (float)(AT)v;
@@ -804,6 +832,11 @@ __global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2)
           if constexpr (NACC == 2) {
             float gq[2];
             gelu2_f(v, gq);
+            if constexpr (DROP) {
+              const uint32_t dk = drop_bits(dr, 1, b, HID, row, nc);
+              gq[0] = drop_f(dr, 1, dk, 0, gq[0]);
+              gq[1] = drop_f(dr, 1, dk, 1, gq[1]);
+            }
             acc1[rb][0][r] = gq[0]; acc1[rb][1][r] = gq[1];
           } else {
 #pragma unroll
@@ -885,8 +918,14 @@ __global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2)
         const float add = tB[row];
         float e[NACC], v[NACC];
         vload<NACC>(&stash[wave][row][NACC * j], e);
+        if constexpr (DROP) {
+          const uint32_t dk = drop_bits(dr, 2, b, 32, row, nc);
+#pragma unroll
+          for (int q = 0; q < NACC; ++q) v[q] = drop_f(dr, 2, dk, q, acc2[q][r] + add) + e[q];
+        } else {
 #pragma unroll
         for (int q = 0; q < NACC; ++q) v[q] = acc2[q][r] + add + e[q];
+        }
         vstore<NACC>(p.y + ob + lane_row, v);
         if (PRE && post) {   // the head sees what a separate launch would read back: the STORED value (bf16 storage: rounded)
 #pragma unroll
@@ -2254,8 +2293,10 @@ struct DwArgsT {
   int B;
 };
 
-template <bool LNB, typename AT>
-__global__ __launch_bounds__(256, 2) void gemm_dw_kernel(DwArgsT<AT> p, int ntiles) {
+template <bool LNB, typename AT, typename... DropX>
+__global__ __launch_bounds__(256, 2) void gemm_dw_kernel(DwArgsT<AT> p, int ntiles, DropX... dx) {
+  constexpr bool DROP = sizeof...(DropX) > 0;   // the block-dropout form (one trailing DropArgs): g is read as M0 s0 g
+  const DropArgs dr = drop_of(dx...);
   constexpr int NACC = 2;
   constexpr int kWave = 64 * kTS;             // floats of one wave's (Gb | Qb) region
   // BXB (bf16 storage): both GEMMs on the bf16 matrix pipe with fp32-accurate products — the activations are exact bf16
@@ -2329,6 +2370,14 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(DwArgsT<AT> p, int ntil
     const unsigned lane_row = (unsigned)(4 * h) * (unsigned)p.V + (unsigned)nc;
     const unsigned lane_par = (unsigned)h * (unsigned)p.V + (unsigned)nc;
     const int64_t sample = (int64_t)b * 32 * p.V;
+    if constexpr (DROP) {   // g_o = M0 s0 g: the input gradient, dW and db all read the operand registers
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+        const uint32_t dk = drop_bits(dr, 0, b, 32, 2 * s + h, nc);
+        bv[s][0] = drop_f(dr, 0, dk, 0, bv[s][0]);
+        bv[s][1] = drop_f(dr, 0, dk, 1, bv[s][1]);
+      }
+    }
 
     // ---- q tile -> Qb (LNB: normalised), in two halves of 8 loads ----
     float mu[NACC] = {0.f, 0.f}, rs[NACC] = {1.f, 1.f};
@@ -3228,9 +3277,30 @@ extern "C" int fz_mlp_supported(int C, int H, int64_t V) {
   return (shape && V > 0 && (V % 4) == 0 && V <= ((int64_t)1 << 27)) ? 1 : 0;
 }
 
+extern "C" int fz_mlp_drop_supported(int C, int H, int64_t V, int products) {
+  return (C == 32 && H == 64 && fz_mlp_supported(C, H, V) && fz_mlp_pre_supported(C, H, V, products) && products_split(products)
+          && knob_chain_fwd_bx()) ? 1 : 0;
+}
+
+static DropArgs drop_args(const uint32_t* m0, const uint32_t* m1, const uint32_t* m2, float s0, float s1, float s2, int64_t V) {
+  DropArgs a;
+  a.m[0] = m0; a.m[1] = m1; a.m[2] = m2;
+  a.s[0] = m0 ? s0 : 1.f; a.s[1] = m1 ? s1 : 1.f; a.s[2] = m2 ? s2 : 1.f;   // (a site without a plane keeps its values)
+  a.nw = (V + 31) / 32;
+  return a;
+}
+static bool drop_scale_ok(const void* m, float s) { return m == nullptr || (s >= 1.f && s < 3.0e38f); }
+
 template <typename AT>
-static int mlp_launch(const fz_mlp_desc* d, fz_stream_t stream) {
+static int mlp_launch(const fz_mlp_desc* d, const fz_mlp_dropout* dd, fz_stream_t stream) {
   if (!fz_mlp_supported(d->C, d->H, d->V)) return fail(FZ_E_UNSUPPORTED, "fz_mlp_chain: needs (C, H) in {(32, 64), (32, 128), (64, 128)}, V % 4 == 0");
+  const bool drop = dd && (dd->m0 || dd->m1 || dd->m2);   // block dropout: the DROP form of mode 0 with pre_in
+  if (drop) {
+    if (!fz_mlp_drop_supported(d->C, d->H, d->V, d->products) || d->mode != 0 || !d->pre_in)
+      return fail(FZ_E_UNSUPPORTED, "fz_mlp_chain: dropout needs (C, H) = (32, 64), split-bf16 products, mode 0 with pre_in (fz_mlp_drop_supported)");
+    if (!drop_scale_ok(dd->m0, dd->s0) || !drop_scale_ok(dd->m1, dd->s1) || !drop_scale_ok(dd->m2, dd->s2))
+      return fail(FZ_E_ARG, "fz_mlp_chain: a dropout scale 1 / (1 - p) must be >= 1 and finite");
+  }
   if (d->C == 64 && d->mode == 2) return fail(FZ_E_UNSUPPORTED, "fz_mlp_chain: the fused weight gradients need C == 32, H == 64");
   if (d->B < 0) return fail(FZ_E_SHAPE, "fz_mlp_chain: negative batch");
   const bool pre = d->pre_in != nullptr;   // the block's out-projection in front of the forward chain (x1 is then an OUTPUT)
@@ -3336,6 +3406,10 @@ static int mlp_launch(const fz_mlp_desc* d, fz_stream_t stream) {
       if (pre) {
         c.preA = (const AT*)d->pre_in; c.preW = d->pre_w; c.preB = d->pre_b; c.preRes = (const AT*)d->pre_res; c.preOut = (AT*)d->pre_out;
         c.postW = d->post_w; c.postB = d->post_b; c.postOut = (AT*)d->post_out; c.postM = d->post_m;
+        if (drop)
+          hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 2, AT, true, true, DropArgs>), dim3((unsigned)(ntiles < wgs2 ? ntiles : wgs2)), block, 0, st, a, c, ntiles,
+                             drop_args(dd->m0, dd->m1, dd->m2, dd->s0, dd->s1, dd->s2, d->V));
+        else
         hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 2, AT, true, true>), dim3((unsigned)(ntiles < wgs2 ? ntiles : wgs2)), block, 0, st, a, c, ntiles);
       } else
       hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 2, AT, true>), dim3((unsigned)(ntiles < wgs2 ? ntiles : wgs2)), block, 0, st, a, c, ntiles);
@@ -3402,7 +3476,11 @@ static int gemm_dw_launch(const fz_gemm_dw_desc* d, fz_stream_t stream) {
   const int rows = fz_gemm_dw_rows(d->B, d->V);
   constexpr int lds = (1536 + 32 + 256 + 4 * 64 * kTS) * (int)sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (d->ln) {
+  if (d->drop_m) {   // site 0 on g (out_proj: no LayerNorm form)
+    auto kern = gemm_dw_kernel<false, AT, DropArgs>;
+    FZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(256), lds, st, a, ntiles, drop_args(d->drop_m, nullptr, nullptr, d->drop_s, 1.f, 1.f, d->V));
+  } else if (d->ln) {
     auto kern = gemm_dw_kernel<true, AT>;
     FZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(256), lds, st, a, ntiles);
@@ -3432,6 +3510,8 @@ extern "C" int fz_gemm_dw(const fz_gemm_dw_desc* d, fz_stream_t stream) {
   if (!d->g || !d->q || !d->w || !d->y || !d->wpart || !d->gw) return fail(FZ_E_ARG, "fz_gemm_dw: null pointer");
   if (d->ln && (!d->stats || !d->ln_g || !d->ln_b || !d->gln)) return fail(FZ_E_ARG, "fz_gemm_dw: the LayerNorm form needs stats, gamma, beta, gln");
   if (!d->ln && d->gadd) return fail(FZ_E_UNSUPPORTED, "fz_gemm_dw: gadd only with the LayerNorm backward");
+  if (d->drop_m && d->ln) return fail(FZ_E_UNSUPPORTED, "fz_gemm_dw: dropout on g only without the LayerNorm backward");
+  if (!drop_scale_ok(d->drop_m, d->drop_s)) return fail(FZ_E_ARG, "fz_gemm_dw: the dropout scale 1 / (1 - p) must be >= 1 and finite");
   if (d->C != 32) return fail(FZ_E_UNSUPPORTED, "fz_gemm_dw: needs C == 32");
   if (d->ldgw != 0 && d->ldgw < 32) return fail(FZ_E_ARG, "fz_gemm_dw: ldgw must be 0 (= 32) or >= 32");
   if (d->ldw != 0 && d->ldw < 32) return fail(FZ_E_ARG, "fz_gemm_dw: ldw must be 0 (= 32) or >= 32");
@@ -3443,7 +3523,14 @@ extern "C" int fz_gemm_dw(const fz_gemm_dw_desc* d, fz_stream_t stream) {
 
 extern "C" int fz_mlp_chain(const fz_mlp_desc* d, fz_stream_t stream) {
   if (!d) return fail(FZ_E_ARG, "fz_mlp_chain: null descriptor");
-  if (d->act_dtype == FZ_STORE_F32) return mlp_launch<float>(d, stream);
-  if (d->act_dtype == FZ_STORE_BF16) return mlp_launch<bf16>(d, stream);
+  if (d->act_dtype == FZ_STORE_F32) return mlp_launch<float>(d, nullptr, stream);
+  if (d->act_dtype == FZ_STORE_BF16) return mlp_launch<bf16>(d, nullptr, stream);
   return fail(FZ_E_ARG, "fz_mlp_chain: act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
+}
+
+extern "C" int fz_mlp_chain_drop(const fz_mlp_desc* d, const fz_mlp_dropout* drop, fz_stream_t stream) {
+  if (!d || !drop) return fail(FZ_E_ARG, "fz_mlp_chain_drop: null descriptor");
+  if (d->act_dtype == FZ_STORE_F32) return mlp_launch<float>(d, drop, stream);
+  if (d->act_dtype == FZ_STORE_BF16) return mlp_launch<bf16>(d, drop, stream);
+  return fail(FZ_E_ARG, "fz_mlp_chain_drop: act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
 }

@@ -596,3 +596,41 @@ def gcorr_mu_update(s, num, r, wT, eps):
     """s ∘ num / (corr(r, wT) + eps) in one launch — for iterations that carry no gradient (inference, or the
     leading `num_iters − num_grad_iters` iterations of deconvolution.py:158-166)."""
     return _gcorr_raw(r.contiguous(), wT.contiguous(), eps, s.contiguous(), num.contiguous())
+
+
+# ---- block dropout masks (csrc/dropout.hip) ---------------------------------------------------------------------------
+def dropout_seed(device):
+    """THE seed draw of one FactorizerBlock forward with live dropout: an int64 tensor (1,) on `device`, drawn by a torch op from
+    that device's default generator — no host sync, `torch.manual_seed` / `torch.cuda.manual_seed` make runs repeat, and
+    consecutive forwards get new masks.  FactorizerBlockFn.forward calls it before anything else in the block touches the
+    generator, so `torch.cuda.manual_seed(s); dropout_seed(dev)` rebuilds the seed (and, through `dropout_keep_bits`, the
+    masks) of a forward run right after the same `torch.cuda.manual_seed(s)`."""
+    return torch.randint(0, 2 ** 62, (1,), device=device, dtype=torch.int64)
+
+
+def dropout_keep_bits(seed, site, B, ch, V, p):
+    """keep bits of dropout site `site` (0: fact.dropout, 1: mlp.block[2], 2: mlp.block[4]) for a (B, ch, V) tensor: int32
+    tensor (B, ch, ceil(V / 32)) holding the uint32 words of fz_dropout_keep_bits (bit v & 31 of word v >> 5)."""
+    lib = N.lib()
+    nw = (int(V) + 31) // 32
+    out = torch.empty((B, ch, nw), dtype=torch.int32, device=seed.device)
+    with _dev_guard(seed):
+        rc = _timed(f"dropout_bits_{ch}", 4 * out.numel(), lambda: lib.fz_dropout_keep_bits(
+            seed.data_ptr(), int(site), int(B), int(ch), int(V), float(p), out.data_ptr(), N.stream_ptr(seed)), cols=B * V)
+    N.check(rc, "fz_dropout_keep_bits")
+    return out
+
+
+def dropout_apply(kind, bits, p, t, aux=None):
+    """y = aux + keep·s·t (N.DROP_RES; aux None: keep·s·t), keep·s·gelu(t) (N.DROP_GELU) or keep·s·t·gelu'(aux)
+    (N.DROP_GELU_BWD) with s = 1 / (1 − p): one pass of fz_dropout_apply over a (B, ch, ...) activation."""
+    B, ch = t.shape[:2]
+    V = t[0, 0].numel() if t.numel() else math.prod(t.shape[2:])
+    y = torch.empty_like(t)
+    n = 2 + (aux is not None)
+    with _dev_guard(t):
+        rc = _timed(f"dropout_apply{kind}_{ch}", n * t.element_size() * t.numel(), lambda: N.lib().fz_dropout_apply(
+            int(kind), bits.data_ptr(), float(p), t.data_ptr(), N.ptr(aux), y.data_ptr(), B, ch, V, N.act_dtype(t),
+            N.stream_ptr(t)), cols=B * V)
+    N.check(rc, "fz_dropout_apply")
+    return y

@@ -179,8 +179,9 @@ def _dw_fused_ok(C, V):
     return C == 32 and V % 4 == 0 and V <= (1 << 27) and os.environ.get("FZ_DW_FUSED", "1") != "0"
 
 
-def _gemm_dw(g, w2, q, ln=None, stats=None, gadd=None, want_bias=False, name="dgrad_wgrad", gw_out=None, gb_out=None):
+def _gemm_dw(g, w2, q, ln=None, stats=None, gadd=None, want_bias=False, name="dgrad_wgrad", gw_out=None, gb_out=None, drop=None):
     """y = Wᵀ g [→ LayerNorm backward + gadd], gw = Σ_v g ⊗ in, gb = Σ_v g — fz_gemm_dw.  ln = (γ, β) or None.
+    drop = (keep bits, p): g is read as keep·g/(1 − p) (block dropout site 0, no ln).
     Returns (y, gw, gb or None, gγ, gβ) (gγ, gβ None without ln)."""
     B, C = q.shape[:2]
     V = _vox(q)
@@ -196,6 +197,8 @@ def _gemm_dw(g, w2, q, ln=None, stats=None, gadd=None, want_bias=False, name="dg
     d.B, d.C, d.V, d.act_dtype = B, C, V, N.act_dtype(q)
     d.ldgw = gw.stride(0)
     d.ldw = w2.stride(0)          # (a 32-column block of a wider weight is read in place)
+    if drop is not None:
+        d.drop_m, d.drop_s = drop[0].data_ptr(), _drop_scale(drop[1])
     gpar = None
     if ln is not None:
         gpar = torch.empty(64, dtype=torch.float32, device=dev)
@@ -208,6 +211,28 @@ def _gemm_dw(g, w2, q, ln=None, stats=None, gadd=None, want_bias=False, name="dg
     if ln is not None:
         return y, gw, gb, gpar[:32], gpar[32:]
     return y, gw, gb, None, None
+
+
+def _drop_scale(p):
+    """1 / (1 − p) of a dropout site as fz_dropout_apply forms it (p rounded to float32 first)"""
+    return 1.0 / (1.0 - float(ctypes.c_float(p).value))
+
+
+def _mlp_dropout(drop):
+    """fz_mlp_dropout of drop = ((bits0, bits1, bits2), (p0, p1, p2)); None entries = site not live"""
+    bits, ps = drop
+    dd = N.MlpDropout()
+    for s in range(3):
+        if bits[s] is not None:
+            setattr(dd, f"m{s}", bits[s].data_ptr())
+            setattr(dd, f"s{s}", _drop_scale(ps[s]))
+    return dd
+
+
+def _mlp_drop_ok(C, Hd, V):
+    """the README block's forward takes its three dropout sites inside the out-projection + MLP chain launch (fz_mlp_chain mode 0)"""
+    return (_outproj_mlp_ok(C, Hd, V)
+            and bool(N.lib().fz_mlp_drop_supported(C, Hd, V, N.products())))
 
 
 def _mlp_chain_ok(C, Hd, V):
@@ -245,7 +270,7 @@ def _outproj_mlp_ok(C, Hd, V):
     return _OUTPROJ_MLP and _mlp_chain_ok(C, Hd, V) and bool(N.lib().fz_mlp_pre_supported(C, Hd, V, N.products()))
 
 
-def _outproj_mlp_fwd_chain(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2, head=None):
+def _outproj_mlp_fwd_chain(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2, head=None, drop=None):
     """x1 = x + out_proj(a) (factorizer.py:53,75) and x2 = x1 + fc2(gelu(fc1(LN(x1)))) (factorizer.py:76; mlp.py:54-63) in ONE
     launch: the out-projection runs on the accumulators in front of the chained MLP GEMMs, x1 is written once (the backward
     needs it) and never read back — 6 instead of 7 tensor passes.  Returns (x1, x2, z1, stats), plus the logits when `head` =
@@ -265,6 +290,7 @@ def _outproj_mlp_fwd_chain(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2,
     d.B, d.C, d.H, d.V = B, C, Hd, V
     d.act_dtype = N.act_dtype(a)
     d.pre_in, d.pre_w, d.pre_b, d.pre_res, d.pre_out = a.data_ptr(), wout2.data_ptr(), _p(bout), x.data_ptr(), x1.data_ptr()
+    dd = _mlp_dropout(drop) if drop is not None else None   # block dropout: the three sites inside this launch
     logits = None
     if head is not None:
         hw, hb = head
@@ -273,7 +299,9 @@ def _outproj_mlp_fwd_chain(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2,
         d.post_w, d.post_b, d.post_out, d.post_m = hw.data_ptr(), _p(hb), logits.data_ptr(), Mh
     with torch.cuda.device(a.device):
         rc = Fn._timed(f"outproj_mlp_chain_fwd_{C}", a.element_size() * (4 * a.numel() + z1.numel() + (logits.numel() if head is not None else 0)),
-                       lambda: N.lib().fz_mlp_chain(ctypes.byref(d), N.stream_ptr(a)), cols=B * V, flops=4 * B * V * C * Hd + 2 * B * V * C * C)
+                       lambda: (N.lib().fz_mlp_chain(ctypes.byref(d), N.stream_ptr(a)) if dd is None
+                                else N.lib().fz_mlp_chain_drop(ctypes.byref(d), ctypes.byref(dd), N.stream_ptr(a))),
+                       cols=B * V, flops=4 * B * V * C * Hd + 2 * B * V * C * C)
     N.check(rc, "fz_mlp_chain")
     if head is not None:
         return x1, x2, z1, st, logits
@@ -1260,6 +1288,47 @@ def cat_linear(x1, x2, w, b=None):
     return linear_cf(torch.cat([x1, x2], dim=1), w, b)
 
 
+# ---- dropout route of the block (training mode, 0 < p < 1 at some site; csrc/dropout.hip) -----------------------------------
+def _block_dropout_bits(x, C, Hd, drop):
+    """(bits0, bits1, bits2): the keep-bit planes of the three sites (None where p = 0), from ONE seed drawn here — the block
+    forward's first use of the device generator (functional.dropout_seed)."""
+    B, V = x.shape[0], _vox(x)
+    seed = Fn.dropout_seed(x.device)
+    return tuple(None if p == 0 else Fn.dropout_keep_bits(seed, s, B, ch, V, p) for s, (ch, p) in enumerate(zip((C, Hd, C), drop)))
+
+
+def _block_dropout_fwd(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2, drop, bits):
+    """steps 3 + 4 of the block with the dropout sites (x1, x2, z1, LayerNorm-2 statistics):
+    x1 = x + M0 s0 (Wo a + bo);  z1 = W1 LN2(x1) + b1;  x2 = x1 + M2 s2 (W2 M1 s1 gelu(z1) + b2).  A site with p = 0 is the
+    plain layer (the residual add and the GELU stay in the GEMM epilogue / operand load)."""
+    B, C = x.shape[:2]
+    V = _vox(x)
+    Hd = w12.shape[0]
+    new = lambda ch: torch.empty((B, ch, *x.shape[2:]), dtype=x.dtype, device=x.device)  # noqa: E731
+    (p0, p1, p2), (m0, m1, m2) = drop, bits
+    if m0 is not None:
+        o = new(C)
+        _gemm([a], wout2, o, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, bias=bout, name="linear")
+        x1 = Fn.dropout_apply(N.DROP_RES, m0, p0, o, x)
+        del o
+    else:
+        x1 = new(C)
+        _gemm([a], wout2, x1, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, bias=bout, res=x, name="act_linear_res")
+    z1 = new(Hd)
+    st2 = torch.empty((B, 2, V), dtype=torch.float32, device=x.device)
+    _gemm([x1], w12, z1, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, bias=b1, ln=(ln_w, ln_b, eps), stats_out=st2, name="ln_linear")
+    h, bact = (Fn.dropout_apply(N.DROP_GELU, m1, p1, z1), ACT["none"]) if m1 is not None else (z1, ACT["gelu"])
+    if m2 is not None:
+        o = new(C)
+        _gemm([h], w22, o, B=B, Cin=Hd, Vin=V, M=C, K=Hd, Ncol=V, bias=b2, bact=bact, name="linear")
+        x2 = Fn.dropout_apply(N.DROP_RES, m2, p2, o, x1)
+        del o
+    else:
+        x2 = new(C)
+        _gemm([h], w22, x2, B=B, Cin=Hd, Vin=V, M=C, K=Hd, Ncol=V, bias=b2, bact=bact, res=x1, name="act_linear_res")
+    return x1, x2, z1, st2
+
+
 # ---- whole FactorizerBlock as ONE autograd node ------------------------------------------------------
 class FactorizerBlockFn(torch.autograd.Function):
     """x → x + out_proj(core(relu(in_proj(LN1(x))))) → (+ MLP(LN2(·)))  (factorizer.py:74-77) with a
@@ -1289,6 +1358,10 @@ class FactorizerBlockFn(torch.autograd.Function):
         w12, w22 = w1.reshape(Hd, C), w2.reshape(C, Hd)
         u0c, v0c = u0.contiguous(), v0.contiguous()
         new = lambda ch: torch.empty((B, ch, *sp), dtype=x.dtype, device=x.device)  # noqa: E731
+        # cfg["drop"] = (p0, p1, p2) of the three dropout sites in training mode (any 0 < p < 1): the seed draw below is the
+        # first use of the device generator in this forward (functional.dropout_seed), the bits are saved for the backward
+        drop = cfg.get("drop")
+        bits = _block_dropout_bits(x, C, Hd, drop) if drop is not None else (None, None, None)
         # 1. t = relu(in_proj(LN1(x)))
         if t_pre is not None:
             t, st1 = t_pre, st_pre
@@ -1308,7 +1381,13 @@ class FactorizerBlockFn(torch.autograd.Function):
             del ym
         # 3. x1 = x + out_proj(a)   4. z1 = fc1(LN2(x1)) ; x2 = x1 + fc2(gelu(z1))
         logits = None
-        if _outproj_mlp_ok(C, Hd, V) and a.is_contiguous() and x.is_contiguous():
+        fused_drop = drop is not None and _mlp_drop_ok(C, Hd, V) and a.is_contiguous()
+        if fused_drop:
+            # the README block: the three masks are read inside the out-projection + MLP chain launch
+            x1, x2, z1, st2 = _outproj_mlp_fwd_chain(a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2, drop=(bits, drop))
+        elif drop is not None:
+            x1, x2, z1, st2 = _block_dropout_fwd(a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2, drop, bits)
+        elif _outproj_mlp_ok(C, Hd, V) and a.is_contiguous() and x.is_contiguous():
             if head_w is not None:
                 x1, x2, z1, st2, logits = _outproj_mlp_fwd_chain(a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2,
                                                                  head=(head_w.reshape(head_w.shape[0], C), head_b))
@@ -1327,7 +1406,7 @@ class FactorizerBlockFn(torch.autograd.Function):
                 x2 = new(C)
                 _gemm([z1], w22, x2, B=B, Cin=Hd, Vin=V, M=C, K=Hd, Ncol=V, bias=b2, bact=ACT["gelu"], res=x1,
                       name="act_linear_res")
-        ctx.save_for_backward(x, st1, t, a, x1, st2, z1, m, n1w, n1b, win2, u0c, v0c, wout2, n2w, n2b, w12, w22)
+        ctx.save_for_backward(x, st1, t, a, x1, st2, z1, m, n1w, n1b, win2, u0c, v0c, wout2, n2w, n2b, w12, w22, *bits)
         ctx.cfg = cfg
         ctx.shapes = (win.shape, wout.shape, w1.shape, w2.shape)
         ctx.prm = tuple(weakref.ref(t) for t in (win, wout, bout, w1, b1, w2, b2))
@@ -1343,8 +1422,9 @@ class FactorizerBlockFn(torch.autograd.Function):
     @staticmethod
     @_bwd
     def backward(ctx, g2, _g_logits=None):
-        x, st1, t, a, x1, st2, z1, m, n1w, n1b, win2, u0c, v0c, wout2, n2w, n2b, w12, w22 = ctx.saved_tensors
+        x, st1, t, a, x1, st2, z1, m, n1w, n1b, win2, u0c, v0c, wout2, n2w, n2b, w12, w22, *bits = ctx.saved_tensors
         cfg = ctx.cfg
+        drop = cfg.get("drop")
         if g2 is None:
             g2 = torch.zeros_like(x)
         g2 = g2.contiguous()
@@ -1373,7 +1453,43 @@ class FactorizerBlockFn(torch.autograd.Function):
 
         # --- MLP ---
         chain = _mlp_chain_ok(C, Hd, V)
-        if _mlp_wgrad_fused_ok(C, Hd, V):
+        go_drop = None
+        if drop is not None:
+            # g_f = M2 s2 g2 feeds fc2's gradients; gz1 = M1 s1 (W2ᵀ g_f) gelu'(z1); dW2 = g_f hᵀ with h = M1 s1 gelu(z1) formed
+            # again from z1 and the saved bits; the residual path of the MLP keeps g2 itself
+            (p0, p1, p2), (m0, m1, m2) = drop, bits
+            gf = Fn.dropout_apply(N.DROP_RES, m2, p2, g2) if m2 is not None else g2
+            gw2 = _GB.out_like(w22)
+            gb2 = torch.empty(C, dtype=torch.float32, device=dev)
+            if m1 is not None:
+                gh = torch.empty_like(z1)
+                _gemm([gf], w22, gh, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, w_t=True, ldw=Hd, name="linear_dgrad")
+                gz1 = Fn.dropout_apply(N.DROP_GELU_BWD, m1, p1, gh, z1)
+                del gh
+                h = Fn.dropout_apply(N.DROP_GELU, m1, p1, z1)
+                wgrad(gf, [h], gw2, B=B, M=C, Cin=Hd, K=Hd, Vq=V, Ncols=V, gbias=gb2, name="wgrad_linear")
+                del h
+            else:
+                gz1 = torch.empty_like(z1)
+                _gemm([gf], w22, gz1, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, w_t=True, ldw=Hd, emul=z1,
+                      emul_kind=ACT["gelu"], name="linear_dgrad")
+                wgrad(gf, [z1], gw2, B=B, M=C, Cin=Hd, K=Hd, Vq=V, Ncols=V, gbias=gb2, qact=ACT["gelu"], name="wgrad_linear")
+            del gf
+            gx1, gg2, gbt2 = _dgrad_lnbwd(gz1, w12, x1, st2, n2w, g2)
+            gw1 = _GB.out_like(w12)
+            gb1 = torch.empty(Hd, dtype=torch.float32, device=dev)
+            wgrad(gz1, [x1], gw1, B=B, M=Hd, Cin=C, K=C, Vq=V, Ncols=V, gbias=gb1, stats=st2, ln=(n2w, n2b),
+                  name="wgrad_ln_linear")
+            del gz1
+            # out_proj sees g_o = M0 s0 gx1 (fz_gemm_dw applies it where it reads g, else one pass here); the LayerNorm-1
+            # backward below adds the unmasked gx1 (the residual path)
+            go = gx1
+            if m0 is not None:
+                if _dw_fused_ok(C, V):
+                    go_drop = (m0, p0)
+                else:
+                    go = Fn.dropout_apply(N.DROP_RES, m0, p0, gx1)
+        elif _mlp_wgrad_fused_ok(C, Hd, V):
             # input-gradient chain + both weight gradients in one pass over (g2, z1, x1)
             gx1, gg2, gbt2, gw1, gb1, gw2, gb2 = _mlp_bwd_chain_wgrad(g2, z1, w12, w22, x1, st2, n2w, n2b)
         else:
@@ -1393,16 +1509,19 @@ class FactorizerBlockFn(torch.autograd.Function):
             wgrad(gz1, [x1], gw1, B=B, M=Hd, Cin=C, K=C, Vq=V, Ncols=V, gbias=gb1, stats=st2, ln=(n2w, n2b),
                    name="wgrad_ln_linear")
             del gz1
+        if drop is None:
+            go = gx1
         # --- out_proj ---
         dw = _dw_fused_ok(C, V)
         if dw:
-            ga, gwo, gbo, _, _ = _gemm_dw(gx1, wout2, a, want_bias=True, name="dgrad_wgrad")
+            ga, gwo, gbo, _, _ = _gemm_dw(go, wout2, a, want_bias=True, name="dgrad_wgrad", drop=go_drop)
         else:
             ga = torch.empty_like(a)
-            _gemm([gx1], wout2, ga, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, w_t=True, ldw=C, name="linear_dgrad")
+            _gemm([go], wout2, ga, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, w_t=True, ldw=C, name="linear_dgrad")
             gwo = _GB.out_like(wout2)
             gbo = torch.empty(C, dtype=torch.float32, device=dev)
-            wgrad(gx1, [a], gwo, B=B, M=C, Cin=C, K=C, Vq=V, Ncols=V, gbias=gbo, name="wgrad_linear")
+            wgrad(go, [a], gwo, B=B, M=C, Cin=C, K=C, Vq=V, Ncols=V, gbias=gbo, name="wgrad_linear")
+        del go
         # --- core (gradient arrives gated by [t > 0]) ---
         if G <= 0:
             gt = torch.zeros_like(t)

@@ -52,8 +52,8 @@ int fz_version(void);
  * compares fz_abi_version() with the FZ_ABI_VERSION of the header it was written against BEFORE the first call and refuses
  * to run on a mismatch (factorizer_amd/_native.py does).  History: 3 = round 3; 4 = round 4 (`products` / `tune` descriptor
  * fields, `products` argument of fz_conv3_*); 5 = round 5 (the two-window entry points fz_nmf_cf_fwd2 / _bwd2 removed, this
- * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw). */
-#define FZ_ABI_VERSION 6
+ * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended). */
+#define FZ_ABI_VERSION 7
 int fz_abi_version(void);
 /* Walking order of the fused-core launches (fz_nmf_cf_fwd / fz_nmf_cf_bwd) this THREAD issues from now on: 0 = ascending over
  * the patch tiles (the default), 1 = descending; < 0 only queries.  Returns the previous setting.  Results do not depend on it.
@@ -351,6 +351,17 @@ typedef struct fz_mlp_desc {
   void* post_out;       /* activation (B, post_m, V) or NULL                                   */
   int post_m;
 } fz_mlp_desc;
+/* [ABI 7] block dropout inside the forward chain: fz_mlp_chain_drop(desc, drop, stream) is fz_mlp_chain with the three sites of
+ * FactorizerBlock applied in the launch, where fz_mlp_drop_supported(C, H, V, products) — (C, H) = (32, 64), split-bf16
+ * products, mode 0 with pre_in:  x1 = x + M0 s0 (pre_w pre_in + pre_b); z1 = W1 LN(x1) + b1 (stored unmasked);
+ * out = x1 + M2 s2 (W2 M1 s1 gelu(z1) + b2).  m* = fz_dropout_keep_bits planes ((B, C), (B, H), (B, C) rows of ceil(V / 32)
+ * uint32 words) or NULL (no dropout at that site); s* = 1 / (1 - p). */
+typedef struct fz_mlp_dropout {
+  const uint32_t* m0;   /* site 0: on the out-projection, before + pre_res */
+  const uint32_t* m1;   /* site 1: on gelu(z1), before fc2                 */
+  const uint32_t* m2;   /* site 2: on fc2's output, before + x1            */
+  float s0, s1, s2;
+} fz_mlp_dropout;
 
 /* ---- input gradient AND weight gradient of a 32 -> 32 1x1 layer in one pass (in_proj behind LayerNorm, out_proj;
  * factorizer.py:38,53 + norm.py:29-34 as autograd sees them):
@@ -378,6 +389,10 @@ typedef struct fz_gemm_dw_desc {
   int act_dtype;
   int ldgw;            /* floats between rows of gw; 0 = 32 (a column block of a wider weight gradient: its width) */
   int ldw;             /* floats between rows of w;  0 = 32 (a column block of a wider weight, read in place)  [ABI 6] */
+  /* [ABI 7] block dropout on g (out_proj under FactorizerBlock site 0; not with ln): the kernel uses drop_s * keep * g for y, gw
+   * and gb; drop_m = a fz_dropout_keep_bits plane (B, 32, ceil(V / 32)) or NULL */
+  const uint32_t* drop_m;
+  float drop_s;
 } fz_gemm_dw_desc;
 int fz_gemm_dw_rows(int B, int64_t V);
 int64_t fz_gemm_dw_workspace_bytes(int B, int64_t V);
@@ -429,10 +444,12 @@ int fz_upcat2(const void* skip, const void* deep, const float* wa, int lda, cons
 
 int fz_mlp_supported(int C, int H, int64_t V);
 int fz_mlp_pre_supported(int C, int H, int64_t V, int products);
+int fz_mlp_drop_supported(int C, int H, int64_t V, int products);   /* [ABI 7] 1: fz_mlp_chain_drop takes this shape */
 int64_t fz_mlp_partials(int B, int64_t V);
 int fz_mlp_wgrad_rows(int B, int64_t V);
 int64_t fz_mlp_wgrad_workspace_bytes(int B, int64_t V);
 int fz_mlp_chain(const fz_mlp_desc* desc, fz_stream_t stream);
+int fz_mlp_chain_drop(const fz_mlp_desc* desc, const fz_mlp_dropout* drop, fz_stream_t stream);   /* [ABI 7] */
 
 /* ---- weight gradients of the GEMM family ------------------------------------------------
  * GW[m,k] = sum_{b,n} P[b,m,n] * Q(In)[b,k,n] — what autograd computes for the weights of
@@ -587,6 +604,27 @@ int fz_sw_finalize(float* out, const float* cnt, int C, int64_t V, fz_stream_t s
 int fz_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                   float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                   fz_stream_t stream);
+
+/* ---- block dropout in training mode (FactorizerBlock: factorizer.py:53-56,69,72; mlp.py:54-60) ----
+ * Sites: 0 = fact.dropout on out_proj(a) + b_out, 1 = mlp.block[2] on gelu(z1), 2 = mlp.block[4] on fc2(h) + b2.
+ * Mask generator: Philox4x32-10 (csrc/fz_philox.h), key = (seed & 0xffffffff, seed >> 32) of the int64 at `seed` (device
+ * memory: read by the kernel, never by the host), counter (v >> 2, c, b, site) for voxel v of channel c of sample b.  The
+ * element is kept iff output word v & 3 < floor((1 - p) 2^32): keep probability exactly that / 2^32; p = 0 keeps all.
+ * Bits: one plane of fz_dropout_bits_words(B, ch, V) uint32 words, (B, ch, ceil(V / 32)) row-major, bit v & 31 of word
+ * v >> 5 of row (b, ch); padding bits are 0.  Returns -1 for a negative shape.
+ * fz_dropout_keep_bits: 0 <= p < 1, site in 0..2, every argument checked on the host before any device work.
+ * fz_dropout_apply: y (B, ch, V activation of act_dtype, V % 4 == 0, 16-byte aligned for fp32 / 8 for bf16), with
+ * s = 1 / (1 - p) and keep = the element's bit:
+ *   FZ_DROP_RES      y = aux + keep s t        (aux NULL: y = keep s t — also the gradient g <- keep s g)
+ *   FZ_DROP_GELU     y = keep s gelu(t)
+ *   FZ_DROP_GELU_BWD y = keep s t gelu'(aux)   (t = dL/dh, aux = z1: dL/dz1) */
+#define FZ_DROP_RES 0
+#define FZ_DROP_GELU 1
+#define FZ_DROP_GELU_BWD 2
+int64_t fz_dropout_bits_words(int B, int ch, int64_t V);
+int fz_dropout_keep_bits(const int64_t* seed, int site, int B, int ch, int64_t V, float p, uint32_t* out, fz_stream_t stream);
+int fz_dropout_apply(int kind, const uint32_t* bits, float p, const void* t, const void* aux, void* y, int B, int ch, int64_t V,
+                     int act_dtype, fz_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("FZ_LIB_PATH") or os.path.join(_HERE, "libfactorizer_h
 FZ_OK = 0
 FZ_E_UNSUPPORTED = -2
 ABI_VERSION = 7   # include/factorizer_hip.h: FZ_ABI_VERSION this binding's argument lists / descriptor layouts are written against
-SOLVER_ID = {"mu": 0, "hals": 1}
+SOLVER_ID = {"mu": 0, "hals": 1, "cd": 2, "smu": 3}
 STORE_F32, STORE_BF16 = 0, 1   # include/factorizer_hip.h: FZ_STORE_*
 PRODUCTS_DEFAULT, PRODUCTS_SPLIT_BF16, PRODUCTS_FP32_MFMA = 0, 1, 2   # FZ_PRODUCTS_*: the `products` field of the descriptors
 _products = threading.local()   # per thread: two models driven from two threads may use different pipes

@@ -32,6 +32,35 @@ int nmf_launch_bwd_r1_bf16(const NmfArgs&);
 int nmf_launch_bwd_r2_bf16(const NmfArgs&);
 int nmf_launch_bwd_r3_bf16(const NmfArgs&);
 int nmf_launch_bwd_r4_bf16(const NmfArgs&);
+// CD and SMU (nmf_r*_cdsmu.hip)
+int nmf_launch_fwd_r1_cdsmu(const NmfArgs&);
+int nmf_launch_fwd_r2_cdsmu(const NmfArgs&);
+int nmf_launch_fwd_r3_cdsmu(const NmfArgs&);
+int nmf_launch_fwd_r4_cdsmu(const NmfArgs&);
+int nmf_launch_bwd_r1_cdsmu(const NmfArgs&);
+int nmf_launch_bwd_r2_cdsmu(const NmfArgs&);
+int nmf_launch_bwd_r3_cdsmu(const NmfArgs&);
+int nmf_launch_bwd_r4_cdsmu(const NmfArgs&);
+int nmf_launch_fwd_r1_bf16_cdsmu(const NmfArgs&);
+int nmf_launch_fwd_r2_bf16_cdsmu(const NmfArgs&);
+int nmf_launch_fwd_r3_bf16_cdsmu(const NmfArgs&);
+int nmf_launch_fwd_r4_bf16_cdsmu(const NmfArgs&);
+int nmf_launch_bwd_r1_bf16_cdsmu(const NmfArgs&);
+int nmf_launch_bwd_r2_bf16_cdsmu(const NmfArgs&);
+int nmf_launch_bwd_r3_bf16_cdsmu(const NmfArgs&);
+int nmf_launch_bwd_r4_bf16_cdsmu(const NmfArgs&);
+
+// the launcher of (direction, storage type, rank) in the CD / SMU units
+static int launch_cdsmu(bool bwd, int act_dtype, int R, const NmfArgs& a) {
+  using L = int (*)(const NmfArgs&);
+  static const L tab[2][2][4] = {
+      {{nmf_launch_fwd_r1_cdsmu, nmf_launch_fwd_r2_cdsmu, nmf_launch_fwd_r3_cdsmu, nmf_launch_fwd_r4_cdsmu},
+       {nmf_launch_fwd_r1_bf16_cdsmu, nmf_launch_fwd_r2_bf16_cdsmu, nmf_launch_fwd_r3_bf16_cdsmu, nmf_launch_fwd_r4_bf16_cdsmu}},
+      {{nmf_launch_bwd_r1_cdsmu, nmf_launch_bwd_r2_cdsmu, nmf_launch_bwd_r3_cdsmu, nmf_launch_bwd_r4_cdsmu},
+       {nmf_launch_bwd_r1_bf16_cdsmu, nmf_launch_bwd_r2_bf16_cdsmu, nmf_launch_bwd_r3_bf16_cdsmu, nmf_launch_bwd_r4_bf16_cdsmu}}};
+  if (act_dtype != FZ_STORE_F32 && act_dtype != FZ_STORE_BF16) return fail(FZ_E_ARG, "fz_nmf: bad act_dtype");
+  return tab[bwd ? 1 : 0][act_dtype == FZ_STORE_BF16 ? 1 : 0][R - 1](a);
+}
 
 static int hist_floats(int M, int N, int R, int G) {
   int MP, NPL;
@@ -52,7 +81,8 @@ static int hist_floats(int M, int N, int R, int G) {
 
 static int check_common(int64_t nmat, int M, int N, int R, int T, int solver) {
   if (nmat < 0 || M < 1 || N < 1 || T < 0) return fz::fail(FZ_E_SHAPE, "fz_nmf: bad sizes");
-  if (solver != FZ_SOLVER_MU && solver != FZ_SOLVER_HALS) return fz::fail(FZ_E_ARG, "fz_nmf: bad solver");
+  if (solver != FZ_SOLVER_MU && solver != FZ_SOLVER_HALS && solver != FZ_SOLVER_CD && solver != FZ_SOLVER_SMU)
+    return fz::fail(FZ_E_ARG, "fz_nmf: bad solver");
   if (R < 1 || R > 4) return fz::fail(FZ_E_UNSUPPORTED, "fz_nmf: rank outside 1..4");
   if (fz::hist_floats(M, N, R, 0) < 0) return fz::fail(FZ_E_UNSUPPORTED, "fz_nmf: (M,N) outside the native kernel families");
   return FZ_OK;
@@ -74,6 +104,7 @@ extern "C" int fz_nmf_fwd(const void* x, const float* u0, const float* v0, void*
   if (nmat == 0) return FZ_OK;
   fz::NmfArgs a{x, u0, v0, nullptr, nullptr, nullptr, y, u_out, v_out, nullptr, nmat, M, N, T, 0, solver, eps,
                 (hipStream_t)stream};
+  if (solver == FZ_SOLVER_CD || solver == FZ_SOLVER_SMU) return fz::launch_cdsmu(false, act_dtype, R, a);
   if (act_dtype == FZ_STORE_BF16) {
     switch (R) {
       case 1: return fz::nmf_launch_fwd_r1_bf16(a);
@@ -101,6 +132,7 @@ extern "C" int fz_nmf_bwd(const void* x, const float* u0, const float* v0, const
   int G = Tgrad < 0 ? 0 : (Tgrad > T ? T : Tgrad);
   fz::NmfArgs a{x, u0, v0, gy, gu, gv, nullptr, nullptr, nullptr, gx, nmat, M, N, T, G, solver, eps,
                 (hipStream_t)stream};
+  if (solver == FZ_SOLVER_CD || solver == FZ_SOLVER_SMU) return fz::launch_cdsmu(true, act_dtype, R, a);
   if (act_dtype == FZ_STORE_BF16) {
     switch (R) {
       case 1: return fz::nmf_launch_bwd_r1_bf16(a);

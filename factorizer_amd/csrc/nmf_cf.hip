@@ -102,8 +102,9 @@ __global__ __launch_bounds__(WPB * 64, (WPB == 8 || R >= 2) ? 2 : 4) void nmf_cf
 
 // backward: gY = gather_w(ga) / W ; gt (+)= [t > 0] ∘ scatter_w(gX)
 template <int R, int SOLVER, typename AT>
-// (launched with 64 .. 256 threads; everything but the hot HALS rank-1 form runs one wave per SIMD rather than spill)
-__global__ __launch_bounds__(256, (R == 1 && SOLVER == 1) ? 2 : 1) void nmf_cf_bwd_kernel(const AT* __restrict__ t, const float* __restrict__ u0,
+// (launched with 64 .. 256 threads; everything but the hot HALS rank-1 form runs one wave per SIMD rather than spill; CD rank 1,
+// the same program without the gate, shares its bound)
+__global__ __launch_bounds__(256, (R == 1 && (SOLVER == SOLVER_HALS || SOLVER == SOLVER_CD)) ? 2 : 1) void nmf_cf_bwd_kernel(const AT* __restrict__ t, const float* __restrict__ u0,
                                                             const float* __restrict__ v0,
                                                             const AT* __restrict__ ga, AT* __restrict__ gt,
                                                             CfGeom q, int64_t nmat, int T, int G, float eps,
@@ -222,7 +223,7 @@ __device__ __forceinline__ void cf_bwd_tile_body(const AT* __restrict__ t, const
 }
 
 template <int R, int SOLVER, int WPB, bool HALF, typename AT>
-__global__ __launch_bounds__(WPB * 64, (R == 1 && SOLVER == 1 && (WPB == 4 || WPB == 1)) ? 2 : 1) void nmf_cf_bwd_tile_kernel(
+__global__ __launch_bounds__(WPB * 64, (R == 1 && (SOLVER == SOLVER_HALS || SOLVER == SOLVER_CD) && (WPB == 4 || WPB == 1)) ? 2 : 1) void nmf_cf_bwd_tile_kernel(
     const AT* __restrict__ t, const float* __restrict__ u0, const float* __restrict__ v0,
     const AT* __restrict__ ga, AT* __restrict__ gt, CfGeom q, int T, int G, float eps, int relu_gate,
     int xcd_remap) {
@@ -272,7 +273,7 @@ static int cf_fwd_launch(const AT* t, const float* u0, const float* v0, AT* out,
   if (rc != FZ_OK) return rc;
   if (!t || !u0 || !v0 || !out) return fail(FZ_E_ARG, "fz_nmf_cf_fwd: null pointer");
   if (R < 1 || R > 2) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_fwd: rank 1..2");
-  if (solver != FZ_SOLVER_MU && solver != FZ_SOLVER_HALS) return fail(FZ_E_ARG, "fz_nmf_cf_fwd: bad solver");
+  if (solver < FZ_SOLVER_MU || solver > FZ_SOLVER_SMU) return fail(FZ_E_ARG, "fz_nmf_cf_fwd: bad solver");
   if (B == 0) return FZ_OK;
   const int64_t nmat = (int64_t)B * q.h * q.G0 * q.G1 * q.G2;
   if (nmat >= (int64_t)1 << 31) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf: more than 2^31 matrices");
@@ -301,15 +302,15 @@ static int cf_fwd_launch(const AT* t, const float* u0, const float* v0, AT* out,
     if (half) { if (twpb == 8) FZ_CF_TILE(RR, SS, 8, true); else if (twpb == 4) FZ_CF_TILE(RR, SS, 4, true); else FZ_CF_TILE(RR, SS, 1, true); } \
     else FZ_CF_TILE(RR, SS, 8, false);                                                                      \
   } while (0)
-    if (R == 1) { if (solver == FZ_SOLVER_MU) FZ_CF_TILE_W(1, SOLVER_MU); else FZ_CF_TILE_W(1, SOLVER_HALS); }
-    else { if (solver == FZ_SOLVER_MU) FZ_CF_TILE_W(2, SOLVER_MU); else FZ_CF_TILE_W(2, SOLVER_HALS); }
+    if (R == 1) { FZ_SOLVER_CASES(FZ_CF_TILE_W, 1); }
+    else { FZ_SOLVER_CASES(FZ_CF_TILE_W, 2); }
     FZ_LAUNCH_CHECK();
     return FZ_OK;
   }
   dim3 grid((unsigned)((nmat + wpb - 1) / wpb)), block(64 * wpb);
 #define FZ_CF_FWD(RR, SS) hipLaunchKernelGGL((nmf_cf_fwd_kernel<RR, SS, AT>), grid, block, 0, st, t, u0, v0, out, q, nmat, T, eps, xr)
-  if (R == 1) { if (solver == FZ_SOLVER_MU) FZ_CF_FWD(1, SOLVER_MU); else FZ_CF_FWD(1, SOLVER_HALS); }
-  else { if (solver == FZ_SOLVER_MU) FZ_CF_FWD(2, SOLVER_MU); else FZ_CF_FWD(2, SOLVER_HALS); }
+  if (R == 1) { FZ_SOLVER_CASES(FZ_CF_FWD, 1); }
+  else { FZ_SOLVER_CASES(FZ_CF_FWD, 2); }
   FZ_LAUNCH_CHECK();
   return FZ_OK;
 }
@@ -335,7 +336,7 @@ static int cf_bwd_launch(const AT* t, const float* u0, const float* v0, const AT
   if (rc != FZ_OK) return rc;
   if (!t || !u0 || !v0 || !ga || !gt) return fail(FZ_E_ARG, "fz_nmf_cf_bwd: null pointer");
   if (R < 1 || R > 2) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_bwd: rank 1..2");
-  if (solver != FZ_SOLVER_MU && solver != FZ_SOLVER_HALS) return fail(FZ_E_ARG, "fz_nmf_cf_bwd: bad solver");
+  if (solver < FZ_SOLVER_MU || solver > FZ_SOLVER_SMU) return fail(FZ_E_ARG, "fz_nmf_cf_bwd: bad solver");
   if (B == 0) return FZ_OK;
   q.gscale_div = (float)(nshift > 1 ? nshift : 1);
   const int G = Tgrad < 0 ? 0 : (Tgrad > T ? T : Tgrad);
@@ -382,8 +383,8 @@ static int cf_bwd_launch(const AT* t, const float* u0, const float* v0, const AT
     if (half) { if (twpb == 4) FZ_CF_BWD_TILE(RR, SS, 4, true); else FZ_CF_BWD_TILE(RR, SS, 1, true); }     \
     else FZ_CF_BWD_TILE(RR, SS, 4, false);                                                                  \
   } while (0)
-      if (R == 1) { if (solver == FZ_SOLVER_MU) FZ_CF_BWD_TILE_W(1, SOLVER_MU); else FZ_CF_BWD_TILE_W(1, SOLVER_HALS); }
-      else { if (solver == FZ_SOLVER_MU) FZ_CF_BWD_TILE_W(2, SOLVER_MU); else FZ_CF_BWD_TILE_W(2, SOLVER_HALS); }
+      if (R == 1) { FZ_SOLVER_CASES(FZ_CF_BWD_TILE_W, 1); }
+      else { FZ_SOLVER_CASES(FZ_CF_BWD_TILE_W, 2); }
       FZ_LAUNCH_CHECK();
       return FZ_OK;
     }
@@ -398,8 +399,8 @@ static int cf_bwd_launch(const AT* t, const float* u0, const float* v0, const AT
                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));                    \
     hipLaunchKernelGGL(kern, grid, block, lds, st, t, u0, v0, ga, gt, q, nmat, T, G, eps, relu_gate, xr);     \
   } while (0)
-  if (R == 1) { if (solver == FZ_SOLVER_MU) FZ_CF_BWD(1, SOLVER_MU); else FZ_CF_BWD(1, SOLVER_HALS); }
-  else { if (solver == FZ_SOLVER_MU) FZ_CF_BWD(2, SOLVER_MU); else FZ_CF_BWD(2, SOLVER_HALS); }
+  if (R == 1) { FZ_SOLVER_CASES(FZ_CF_BWD, 1); }
+  else { FZ_SOLVER_CASES(FZ_CF_BWD, 2); }
   FZ_LAUNCH_CHECK();
   return FZ_OK;
 }

@@ -14,8 +14,10 @@
 // Update rules restated from the reference (paths relative to the reference root):
 //   MU   factorization/matrix_factorization.py:241-247
 //   HALS factorization/matrix_factorization.py:210-229 (CoordinateDescent, project=ReLU)
+//   CD   factorization/matrix_factorization.py:210-229 (CoordinateDescent, project=Identity)
+//   SMU  factorization/matrix_factorization.py:319-341 (SemiMultiplicativeUpdate; X of any sign)
 //   alternation U then V with the new U: :122-136 ; reconstruct u @ v.mT: :532-533
-// Reverse sweep: SURVEY.md Appendix A (hand-derived; checked against autograd by the oracle).
+// Reverse sweep: SURVEY.md Appendix A (hand-derived; checked against autograd by the oracle); CD / SMU: DESIGN.md §7.1.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -28,13 +30,32 @@ namespace fz {
 
 constexpr int SOLVER_MU = 0;
 constexpr int SOLVER_HALS = 1;
+constexpr int SOLVER_CD = 2;
+constexpr int SOLVER_SMU = 3;
+template <int SOLVER>
+constexpr bool fz_known_solver() { return SOLVER == SOLVER_MU || SOLVER == SOLVER_HALS || SOLVER == SOLVER_CD || SOLVER == SOLVER_SMU; }
+
+// host dispatch of a launch macro on the run-time id `solver` (FZ_SOLVER_*, checked by the entry point):
+// MACRO(args..., SOLVER_x); an id the entry point let through that is none of MU / CD / SMU runs HALS, as before CD / SMU.
+#define FZ_SOLVER_CASES(MACRO, ...)                                         \
+  do {                                                                      \
+    switch (solver) {                                                       \
+      case FZ_SOLVER_MU: MACRO(__VA_ARGS__, SOLVER_MU); break;              \
+      case FZ_SOLVER_CD: MACRO(__VA_ARGS__, SOLVER_CD); break;              \
+      case FZ_SOLVER_SMU: MACRO(__VA_ARGS__, SOLVER_SMU); break;            \
+      default: MACRO(__VA_ARGS__, SOLVER_HALS); break;                      \
+    }                                                                       \
+  } while (0)
 
 // reciprocal: v_rcp_f32 on device (1 ulp) instead of the ~10-instruction IEEE division sequence —
 // the HALS/MU ratios need 1e-4 parity, not correct rounding, and the backward kernel is VALU-bound
 #if defined(__HIP_DEVICE_COMPILE__)
 FZ_HD float fz_rcp(float v) { return __builtin_amdgcn_rcpf(v); }
+// square root of the SMU ratio n/d (n, d >= eps): v_sqrt_f32 (1 ulp), same reasoning as fz_rcp
+FZ_HD float fz_sqrt(float v) { return __builtin_amdgcn_sqrtf(v); }
 #else
 FZ_HD float fz_rcp(float v) { return 1.0f / v; }
+FZ_HD float fz_sqrt(float v) { return __builtin_sqrtf(v); }
 #endif
 FZ_HD float fz_relu(float v) { return v > 0.f ? v : 0.f; }
 // gate(w, g) = g where w > 0 else 0  (ReLU mask taken from the forward value)
@@ -81,7 +102,8 @@ FZ_HD void sum_all(W& w, F (&acc)[K]) {
 // ---- one half-step on K independent rows of a factor:  w' = update(w; a, b) ------------
 template <int K, int R, int SOLVER, class F>
 FZ_HD void update_rows(F (&w)[K][R], const F (&a)[K][R], const F (&b)[R][R], float eps) {
-  if (SOLVER == SOLVER_MU) {
+  static_assert(fz_known_solver<SOLVER>(), "update_rows: unknown solver id");
+  if constexpr (SOLVER == SOLVER_MU) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       F nw[R];
@@ -95,7 +117,37 @@ FZ_HD void update_rows(F (&w)[K][R], const F (&a)[K][R], const F (&b)[R][R], flo
 #pragma unroll
       for (int r = 0; r < R; ++r) w[k][r] = nw[r];
     }
+  } else if constexpr (SOLVER == SOLVER_SMU) {
+    // semi-NMF: n = relu(a) + w relu(-b) + eps, d = relu(-a) + w relu(b) + eps, w' = w sqrt(n / d) (Jacobi: the old w
+    // throughout the row).  The split of b by sign is shared by all K rows.
+    F bpos[R][R], bneg[R][R];
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        bpos[q][r] = fz_relu(b[q][r]);
+        bneg[q][r] = fz_relu(F(0.f) - b[q][r]);
+      }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      F nw[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        F nu = fz_relu(a[k][r]);
+        F de = fz_relu(F(0.f) - a[k][r]);
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+          nu = nu + w[k][q] * bneg[q][r];
+          de = de + w[k][q] * bpos[q][r];
+        }
+        nw[r] = w[k][r] * fz_sqrt((nu + eps) * fz_rcp(de + eps));
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) w[k][r] = nw[r];
+    }
   } else {
+    // HALS, and CD (the same rule without the projection)
+    constexpr bool kProj = SOLVER == SOLVER_HALS;
     // the denominators b[r][r] + eps are shared by all K rows: one reciprocal per column
     F inv[R];
 #pragma unroll
@@ -103,7 +155,9 @@ FZ_HD void update_rows(F (&w)[K][R], const F (&a)[K][R], const F (&b)[R][R], flo
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       if (R == 1) {
-        w[k][0] = fz_relu((a[k][0] + eps) * inv[0]);
+        const F t = (a[k][0] + eps) * inv[0];
+        if constexpr (kProj) w[k][0] = fz_relu(t);
+        else w[k][0] = t;
       } else {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -116,7 +170,9 @@ FZ_HD void update_rows(F (&w)[K][R], const F (&a)[K][R], const F (&b)[R][R], flo
             s = first ? t : s + t;
             first = false;
           }
-          w[k][r] = fz_relu((a[k][r] - s + eps) * inv[r]);
+          const F t = (a[k][r] - s + eps) * inv[r];
+          if constexpr (kProj) w[k][r] = fz_relu(t);
+          else w[k][r] = t;
         }
       }
     }
@@ -130,7 +186,8 @@ template <int R, int SOLVER, class F>
 FZ_HD void half_bwd_row(const F (&wold)[R], const F (&wnew)[R], const F (&a)[R],
                         const F (&b)[R][R], F (&gwn)[R], F (&gwo)[R], F (&ga)[R],
                         F (&gb)[R][R], float eps) {
-  if (SOLVER == SOLVER_MU) {
+  static_assert(fz_known_solver<SOLVER>(), "half_bwd_row: unknown solver id");
+  if constexpr (SOLVER == SOLVER_MU) {
     F gn[R], gdn[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -151,13 +208,48 @@ FZ_HD void half_bwd_row(const F (&wold)[R], const F (&wnew)[R], const F (&a)[R],
 #pragma unroll
       for (int q = 0; q < R; ++q) gb[q][r] = gb[q][r] + wold[q] * gdn[r];
     }
+  } else if constexpr (SOLVER == SOLVER_SMU) {
+    // w'_r = w_r s_r, s_r = sqrt(n_r / d_r):  gn_r = g_r w'_r / (2 n_r), gd_r = -g_r w'_r / (2 d_r),
+    // dL/dw_r = g_r s_r + sum_c (gn_c relu(-b_rc) + gd_c relu(b_rc)),  dL/da_r = gn_r [a_r > 0] - gd_r [a_r < 0],
+    // dL/db_qr += w_q (gd_r [b_qr > 0] - gn_r [b_qr < 0])   (relu'(0) = 0)
+    F gn[R], gd[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      F nu = fz_relu(a[r]);
+      F de = fz_relu(F(0.f) - a[r]);
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        nu = nu + wold[q] * fz_relu(F(0.f) - b[q][r]);
+        de = de + wold[q] * fz_relu(b[q][r]);
+      }
+      const F ide = fz_rcp(de + eps);
+      const F inu = fz_rcp(nu + eps);
+      const F h = gwn[r] * wnew[r] * 0.5f;
+      gwo[r] = gwn[r] * fz_sqrt((nu + eps) * ide);
+      gn[r] = h * inu;
+      gd[r] = F(0.f) - h * ide;
+      ga[r] = fz_gate(a[r], gn[r]) - fz_gate(F(0.f) - a[r], gd[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      F t = gwo[r];
+#pragma unroll
+      for (int c = 0; c < R; ++c) t = t + gn[c] * fz_relu(F(0.f) - b[r][c]) + gd[c] * fz_relu(b[r][c]);
+      gwo[r] = t;
+#pragma unroll
+      for (int q = 0; q < R; ++q)
+        gb[q][r] = gb[q][r] + wold[q] * (fz_gate(b[q][r], gd[r]) - fz_gate(F(0.f) - b[q][r], gn[r]));
+    }
   } else {
+    // HALS, and CD: the same reverse step without the ReLU gate
 #pragma unroll
     for (int r = 0; r < R; ++r) gwo[r] = F(0.f);
 #pragma unroll
     for (int r = R - 1; r >= 0; --r) {
       const F iden = fz_rcp(b[r][r] + eps);
-      F gq = fz_gate(wnew[r], gwn[r]);
+      F gq;
+      if constexpr (SOLVER == SOLVER_HALS) gq = fz_gate(wnew[r], gwn[r]);
+      else gq = gwn[r];
       F gnum = gq * iden;
       gb[r][r] = gb[r][r] - (gq * wnew[r]) * iden;
       ga[r] = gnum;
@@ -427,8 +519,14 @@ FZ_HD void nmf_backward_wave(W& w, const float* u0, const float* v0,
   using F = typename W::F;
   // The reverse sweep on distributed rows adds the rows' contributions to dL/db in a tree over the lane groups instead of
   // row by row.  MU keeps the row-by-row (uniform) reverse sweep (its ε⁻¹-scaled gradients are the most sensitive to
-  // rounding order in the oracle tests); its forward recomputation is distributed where the policy asks for it.
-  constexpr bool kDistBwd = DistRows<W>::value && M == 8 && SOLVER != SOLVER_MU;
+  // rounding order in the oracle tests); its forward recomputation is distributed where the policy asks for it.  SMU keeps it
+  // too, for the same reason: its reverse step scales by 1 / (2 n) and 1 / (2 d), which sit at eps for rows whose numerator or
+  // denominator vanishes.  CD has HALS's reverse step without the gate and takes the distributed sweep like HALS.
+  constexpr bool kDistBwd = DistRows<W>::value && M == 8 && SOLVER != SOLVER_MU && SOLVER != SOLVER_SMU;
+  // MU and HALS give a padded row / column (forced to zero by the forward) a zero gradient through their algebra or the ReLU
+  // gate whatever arrives there; CD (no gate) and SMU (the sqrt(n / d) factor) would pass it on, so their incoming gradients
+  // are masked once here, and the sweep keeps them zero (x, u and v vanish on the padding).
+  constexpr bool kMaskPad = SOLVER == SOLVER_CD || SOLVER == SOLVER_SMU;
   F gu[M][R];
   F gud[R];      // (kDistBwd) dL/du in distributed form: lane group m holds row m
   F gv[NPL][R];
@@ -474,7 +572,19 @@ FZ_HD void nmf_backward_wave(W& w, const float* u0, const float* v0,
         for (int m = 1; m < M; ++m) acc = acc + g[m][j] * u[m][r];
         gv[j][r] = acc;
         if (gv_ext != nullptr) gv[j][r] = gv[j][r] + w.ld_v0(gv_ext, j, r, R);
+        if constexpr (kMaskPad) gv[j][r] = w.keep_col(j, gv[j][r]);
       }
+    if constexpr (kMaskPad) {
+      if constexpr (kDistBwd) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) gud[r] = w.grp_below(mreal) ? gud[r] : F(0.f);
+      } else {
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+          for (int r = 0; r < R; ++r) gu[m][r] = (m < mreal) ? gu[m][r] : F(0.f);
+      }
+    }
   }
 #pragma unroll
   for (int m = 0; m < M; ++m)

@@ -701,30 +701,27 @@ extern "C" int fz_gnmf_launches(int T, int Tgrad, int backward) {
   return backward ? fwd + 2 * G + 1 : fwd;
 }
 
+#define FZ_GN_RANKS(CALL, SS)                                                                        \
+  switch (R) {                                                                                       \
+    case 1: return v4 ? CALL(1, SS, 4) : CALL(1, SS, 1);                                             \
+    case 2: return v4 ? CALL(2, SS, 4) : CALL(2, SS, 1);                                             \
+    case 3: return v4 ? CALL(3, SS, 4) : CALL(3, SS, 1);                                             \
+    default: return v4 ? CALL(4, SS, 4) : CALL(4, SS, 1);                                            \
+  }
 #define FZ_GN_DISPATCH(CALL)                                                                         \
   do {                                                                                               \
     const bool v4 = (N % 4) == 0;                                                                    \
-    if (solver == FZ_SOLVER_MU) {                                                                    \
-      switch (R) {                                                                                   \
-        case 1: return v4 ? CALL(1, SOLVER_MU, 4) : CALL(1, SOLVER_MU, 1);                           \
-        case 2: return v4 ? CALL(2, SOLVER_MU, 4) : CALL(2, SOLVER_MU, 1);                           \
-        case 3: return v4 ? CALL(3, SOLVER_MU, 4) : CALL(3, SOLVER_MU, 1);                           \
-        default: return v4 ? CALL(4, SOLVER_MU, 4) : CALL(4, SOLVER_MU, 1);                          \
-      }                                                                                              \
-    }                                                                                                \
-    switch (R) {                                                                                     \
-      case 1: return v4 ? CALL(1, SOLVER_HALS, 4) : CALL(1, SOLVER_HALS, 1);                         \
-      case 2: return v4 ? CALL(2, SOLVER_HALS, 4) : CALL(2, SOLVER_HALS, 1);                         \
-      case 3: return v4 ? CALL(3, SOLVER_HALS, 4) : CALL(3, SOLVER_HALS, 1);                         \
-      default: return v4 ? CALL(4, SOLVER_HALS, 4) : CALL(4, SOLVER_HALS, 1);                        \
-    }                                                                                                \
+    if (solver == FZ_SOLVER_MU) FZ_GN_RANKS(CALL, SOLVER_MU)                                         \
+    if (solver == FZ_SOLVER_CD) FZ_GN_RANKS(CALL, SOLVER_CD)                                         \
+    if (solver == FZ_SOLVER_SMU) FZ_GN_RANKS(CALL, SOLVER_SMU)                                       \
+    FZ_GN_RANKS(CALL, SOLVER_HALS)                                                                   \
   } while (0)
 
 extern "C" int fz_gnmf_fwd(const float* x, const float* u0, const float* v0, float* y, float* u_out, float* v_out,
                            int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, void* workspace,
                            fz_stream_t stream) {
   if (!fz_gnmf_supported(M, N, R, T, T)) return fail(FZ_E_UNSUPPORTED, "fz_gnmf_fwd: needs 1 <= M <= 64, 1 <= R <= 4");
-  if (solver != FZ_SOLVER_MU && solver != FZ_SOLVER_HALS) return fail(FZ_E_ARG, "fz_gnmf_fwd: bad solver");
+  if (solver < FZ_SOLVER_MU || solver > FZ_SOLVER_SMU) return fail(FZ_E_ARG, "fz_gnmf_fwd: bad solver");
   if (nmat < 0 || nmat > 65535) return fail(FZ_E_SHAPE, "fz_gnmf_fwd: 0 <= nmat <= 65535");
   if (!x || !u0 || !v0 || !y || !workspace) return fail(FZ_E_ARG, "fz_gnmf_fwd: null pointer");
   if (nmat == 0) return FZ_OK;
@@ -739,7 +736,7 @@ extern "C" int fz_gnmf_bwd(const float* x, const float* u0, const float* v0, con
                            const float* gv, float* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad,
                            int solver, float eps, void* workspace, fz_stream_t stream) {
   if (!fz_gnmf_supported(M, N, R, T, Tgrad)) return fail(FZ_E_UNSUPPORTED, "fz_gnmf_bwd: needs 1 <= M <= 64, 1 <= R <= 4");
-  if (solver != FZ_SOLVER_MU && solver != FZ_SOLVER_HALS) return fail(FZ_E_ARG, "fz_gnmf_bwd: bad solver");
+  if (solver < FZ_SOLVER_MU || solver > FZ_SOLVER_SMU) return fail(FZ_E_ARG, "fz_gnmf_bwd: bad solver");
   if (nmat < 0 || nmat > 65535) return fail(FZ_E_SHAPE, "fz_gnmf_bwd: 0 <= nmat <= 65535");
   if (!x || !u0 || !v0 || !gx || !workspace || (!gy && !gu && !gv)) return fail(FZ_E_ARG, "fz_gnmf_bwd: null pointer");
   const int G = Tgrad < 0 ? 0 : (Tgrad > T ? T : Tgrad);

@@ -1,7 +1,8 @@
 // nmf_kernels.inc — gfx950 kernels around the per-wave program of nmf_core.h.
 // Included by nmf_r{1..4}.hip / nmf_r{1..4}_bf16.hip with FZ_R (rank) and FZ_AT (storage type of the
 // matrices X / Y / GY / GX: float or bf16) defined — one translation unit per (rank, storage type)
-// keeps the build parallel.  Whatever the storage type, the wave program runs in fp32: the factors,
+// keeps the build parallel.  Those units instantiate MU and HALS; nmf_r{1..4}[_bf16]_cdsmu.hip define
+// FZ_NMF_CD_SMU and instantiate CD and SMU.  Whatever the storage type, the wave program runs in fp32: the factors,
 // Gram matrices and eps of matrix_factorization.py:200,236 never see bf16 (SURVEY.md §5).  Replaces the reference's per-iteration bmm + elementwise launches
 // (factorization/matrix_factorization.py:213-227, 241-247, 514-546).
 #include "fz_common.h"
@@ -231,9 +232,19 @@ static int launch_bwd_t(const NmfArgs& a) {
 
 template <bool BWD, int M, int NPL, bool FAST>
 static int launch_solver(const NmfArgs& a) {
+#if FZ_NMF_CD_SMU
+  // the CD / SMU units (nmf_r*_cdsmu.hip): their own translation units, so the MU / HALS objects stay as they were and the
+  // build stays parallel
+  if (a.solver == FZ_SOLVER_CD)
+    return BWD ? launch_bwd_t<M, NPL, SOLVER_CD, FAST>(a) : launch_fwd_t<M, NPL, SOLVER_CD, FAST>(a);
+  if (a.solver == FZ_SOLVER_SMU)
+    return BWD ? launch_bwd_t<M, NPL, SOLVER_SMU, FAST>(a) : launch_fwd_t<M, NPL, SOLVER_SMU, FAST>(a);
+  return fail(FZ_E_ARG, "fz_nmf: bad solver");
+#else
   if (a.solver == FZ_SOLVER_MU)
     return BWD ? launch_bwd_t<M, NPL, SOLVER_MU, FAST>(a) : launch_fwd_t<M, NPL, SOLVER_MU, FAST>(a);
   return BWD ? launch_bwd_t<M, NPL, SOLVER_HALS, FAST>(a) : launch_fwd_t<M, NPL, SOLVER_HALS, FAST>(a);
+#endif
 }
 
 template <bool BWD>

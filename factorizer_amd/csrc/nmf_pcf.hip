@@ -381,8 +381,8 @@ static int pcf_fwd_launch(const AT* t, const float* u0, const float* v0, AT* out
   if (half_on && q.P > 128 && q.P <= 160) {
     dim3 grid2((unsigned)(((nmat + 1) / 2 + 3) / 4));
 #define FZ_PCF_FWD2(RR, SS) hipLaunchKernelGGL((nmf_pcf_fwd2_kernel<5, RR, SS, AT>), grid2, block, 0, st, t, u0, v0, out, q, nmat, T, eps)
-    if (R == 1) { if (solver == FZ_SOLVER_MU) FZ_PCF_FWD2(1, SOLVER_MU); else FZ_PCF_FWD2(1, SOLVER_HALS); }
-    else { if (solver == FZ_SOLVER_MU) FZ_PCF_FWD2(2, SOLVER_MU); else FZ_PCF_FWD2(2, SOLVER_HALS); }
+    if (R == 1) { FZ_SOLVER_CASES(FZ_PCF_FWD2, 1); }
+    else { FZ_SOLVER_CASES(FZ_PCF_FWD2, 2); }
 #undef FZ_PCF_FWD2
     FZ_LAUNCH_CHECK();
     return FZ_OK;
@@ -390,8 +390,8 @@ static int pcf_fwd_launch(const AT* t, const float* u0, const float* v0, AT* out
 #define FZ_PCF_FWD(NN, RR, SS) hipLaunchKernelGGL((nmf_pcf_fwd_kernel<NN, RR, SS, AT>), grid, block, 0, st, t, u0, v0, out, q, nmat, T, eps)
 #define FZ_PCF_FWD_RS(NN)                                                                                    \
   do {                                                                                                       \
-    if (R == 1) { if (solver == FZ_SOLVER_MU) FZ_PCF_FWD(NN, 1, SOLVER_MU); else FZ_PCF_FWD(NN, 1, SOLVER_HALS); } \
-    else { if (solver == FZ_SOLVER_MU) FZ_PCF_FWD(NN, 2, SOLVER_MU); else FZ_PCF_FWD(NN, 2, SOLVER_HALS); }  \
+    if (R == 1) { FZ_SOLVER_CASES(FZ_PCF_FWD, NN, 1); } \
+    else { FZ_SOLVER_CASES(FZ_PCF_FWD, NN, 2); }  \
   } while (0)
   switch (pcf_npl(q.P)) {
     case 1: FZ_PCF_FWD_RS(1); break;
@@ -424,8 +424,8 @@ static int pcf_bwd_launch(const AT* t, const float* u0, const float* v0, const A
       FZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds2)); \
     hipLaunchKernelGGL(kern, grid2, block2, lds2, st, t, u0, v0, ga, gt, q, nmat, T, G, eps, relu_gate);      \
   } while (0)
-    if (R == 1) { if (solver == FZ_SOLVER_MU) FZ_PCF_BWD2(1, SOLVER_MU); else FZ_PCF_BWD2(1, SOLVER_HALS); }
-    else { if (solver == FZ_SOLVER_MU) FZ_PCF_BWD2(2, SOLVER_MU); else FZ_PCF_BWD2(2, SOLVER_HALS); }
+    if (R == 1) { FZ_SOLVER_CASES(FZ_PCF_BWD2, 1); }
+    else { FZ_SOLVER_CASES(FZ_PCF_BWD2, 2); }
 #undef FZ_PCF_BWD2
     FZ_LAUNCH_CHECK();
     return FZ_OK;
@@ -444,8 +444,8 @@ static int pcf_bwd_launch(const AT* t, const float* u0, const float* v0, const A
   } while (0)
 #define FZ_PCF_BWD_RS(NN)                                                                                     \
   do {                                                                                                        \
-    if (R == 1) { if (solver == FZ_SOLVER_MU) FZ_PCF_BWD(NN, 1, SOLVER_MU); else FZ_PCF_BWD(NN, 1, SOLVER_HALS); } \
-    else { if (solver == FZ_SOLVER_MU) FZ_PCF_BWD(NN, 2, SOLVER_MU); else FZ_PCF_BWD(NN, 2, SOLVER_HALS); }   \
+    if (R == 1) { FZ_SOLVER_CASES(FZ_PCF_BWD, NN, 1); } \
+    else { FZ_SOLVER_CASES(FZ_PCF_BWD, NN, 2); }   \
   } while (0)
   switch (pcf_npl(q.P)) {
     case 1: FZ_PCF_BWD_RS(1); break;
@@ -497,7 +497,7 @@ extern "C" int fz_nmf_pcf_fwd(const void* t, const float* u0, const float* v0, v
   if (rc != FZ_OK) return rc;
   if (!t || !u0 || !v0 || !out) return fail(FZ_E_ARG, "fz_nmf_pcf_fwd: null pointer");
   if (R < 1 || R > 2) return fail(FZ_E_UNSUPPORTED, "fz_nmf_pcf_fwd: rank 1..2");
-  if (solver != FZ_SOLVER_MU && solver != FZ_SOLVER_HALS) return fail(FZ_E_ARG, "fz_nmf_pcf_fwd: bad solver");
+  if (solver < FZ_SOLVER_MU || solver > FZ_SOLVER_SMU) return fail(FZ_E_ARG, "fz_nmf_pcf_fwd: bad solver");
   if (B == 0) return FZ_OK;
   hipStream_t st = (hipStream_t)stream;
   if (act_dtype == FZ_STORE_F32) return pcf_fwd_launch<float>((const float*)t, u0, v0, (float*)out, q, R, T, solver, eps, st);
@@ -513,7 +513,7 @@ extern "C" int fz_nmf_pcf_bwd(const void* t, const float* u0, const float* v0, c
   if (rc != FZ_OK) return rc;
   if (!t || !u0 || !v0 || !ga || !gt) return fail(FZ_E_ARG, "fz_nmf_pcf_bwd: null pointer");
   if (R < 1 || R > 2) return fail(FZ_E_UNSUPPORTED, "fz_nmf_pcf_bwd: rank 1..2");
-  if (solver != FZ_SOLVER_MU && solver != FZ_SOLVER_HALS) return fail(FZ_E_ARG, "fz_nmf_pcf_bwd: bad solver");
+  if (solver < FZ_SOLVER_MU || solver > FZ_SOLVER_SMU) return fail(FZ_E_ARG, "fz_nmf_pcf_bwd: bad solver");
   if (B == 0) return FZ_OK;
   q.gscale_div = (float)(nshift > 1 ? nshift : 1);
   const int G = Tgrad < 0 ? 0 : (Tgrad > T ? T : Tgrad);

@@ -49,7 +49,7 @@ class RandomInit(Initializer):
         return self.u0.expand(*lead, *self.u0.shape), self.v0.expand(*lead, *self.v0.shape)
 
 
-# ---- solvers (composed form; the device kernels implement MU and HALS natively) ------------
+# ---- solvers (composed form; the device kernels implement MU, HALS, CD and SMU natively) ----
 class BCDSolver(nn.Module):
     """Block-coordinate alternation: factor order (0,1) = U then V, V sees the new U
     (matrix_factorization.py:108-136)."""
@@ -94,7 +94,10 @@ class CoordinateDescent(BCDSolver):
 
     @property
     def native_id(self):
-        return "hals" if isinstance(self.project, nn.ReLU) else None
+        # ReLU projection: HALS; no projection: the unprojected rule ("cd"); any other projection stays composed
+        if isinstance(self.project, nn.ReLU):
+            return "hals"
+        return "cd" if isinstance(self.project, nn.Identity) else None
 
     def update_u(self, x, u, v):
         return composed.cd_update(x, u, v, self.eps, self.project)
@@ -200,6 +203,7 @@ class WeightedMultiplicativeUpdate(BCDSolver):
 class SemiMultiplicativeUpdate(BCDSolver):
     """Semi-NMF update (X of any sign, the updated factor >= 0), matrix_factorization.py:319-341:
     U <- U ∘ sqrt((a+ + U b-) / (a- + U b+)) with a = XV, b = V^T V split into positive/negative parts."""
+    native_id = "smu"
 
     def __init__(self, factor=(0, 1), eps: float = 1e-16, **kwargs):
         super().__init__(factor=factor)

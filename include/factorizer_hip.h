@@ -42,6 +42,9 @@ extern "C" {
 
 #define FZ_SOLVER_MU 0   /* matrix_factorization.py:232-247 MultiplicativeUpdate        */
 #define FZ_SOLVER_HALS 1 /* matrix_factorization.py:194-229 CoordinateDescent + ReLU    */
+#define FZ_SOLVER_CD 2   /* matrix_factorization.py:194-229 CoordinateDescent, no projection (X, U, V of any sign) */
+#define FZ_SOLVER_SMU 3  /* matrix_factorization.py:319-341 SemiMultiplicativeUpdate (X of any sign) */
+/* Every NMF entry point takes one of these four; an older library rejects CD / SMU with FZ_E_ARG ("bad solver"). */
 
 typedef void* fz_stream_t; /* hipStream_t */
 

@@ -386,12 +386,43 @@ def g10():
     npz("g10_lower_d", **arrs)
 
 
+# ---- G11: the cd / smu solvers across the wave-program shape families (matrix_factorization.py:194-229, 319-341) --------------
+def g11():
+    """cd (init "normal") and smu (init "uniform", non-negative and signed X) on 8x512, 8x150, 5x100 and 16x256: each variant
+    covers ranks 1-4, 5 and 10 iterations and fewer graded than total iterations, the four shapes between them (the two large
+    shapes once each: the float64 sweep of tests/test_nmf_solvers_cpu.py covers them for both solvers); u, v, y and
+    dL/dx of the reference's own autograd.  One matrix per case, and X, dL/dy and the initial factors on a 2^-6 grid (exact
+    in fp32, they compress), so the file stays small."""
+    arrs = {}
+    variants = {"cd": ("cd", "normal", False), "smu": ("smu", "uniform", False), "smus": ("smu", "uniform", True)}
+    cases = {  # (M, N, R, T, G)
+        "cd": [(8, 512, 1, 5, 5), (8, 150, 2, 10, 8), (5, 100, 3, 5, 3), (5, 100, 4, 10, 10)],
+        "smu": [(8, 150, 2, 10, 8), (8, 150, 3, 5, 5), (5, 100, 4, 10, 10), (5, 100, 1, 5, 3)],
+        "smus": [(16, 256, 2, 10, 8), (8, 150, 4, 5, 5), (5, 100, 1, 10, 10), (5, 100, 3, 5, 3)],
+    }
+    q = lambda t: torch.round(t * 64) / 64
+    for vname, (solver, init, signed) in variants.items():
+        for i, (M, N, R, T, G) in enumerate(cases[vname]):
+            name = f"{vname}_{M}x{N}_r{R}_t{T}_g{G}"
+            torch.manual_seed(100 * i + 10 * R + len(vname))
+            mf = ft.MatrixFactorization(size=(M, N), rank=R, num_iters=T, num_grad_steps=G, init=init, solver=solver)
+            x = q(torch.randn(1, M, N) if signed else torch.rand(1, M, N)).requires_grad_(True)
+            with torch.no_grad():   # (no exact zero in the initial factors: a multiplicative update never leaves it)
+                for buf in (mf.init.u0, mf.init.v0):
+                    buf.copy_(torch.where(q(buf) == 0, torch.full_like(buf, 1 / 64), q(buf)))
+            u0, v0 = mf.init(x)
+            u, v = mf.decompose(x)
+            y = mf.reconstruct(u, v)
+            gy = q(torch.rand_like(y) - 0.5)
+            (gx,) = torch.autograd.grad(y, x, gy)
+            arrs.update({f"{name}:x": x, f"{name}:u0": u0[0], f"{name}:v0": v0[0], f"{name}:u": u, f"{name}:v": v,
+                         f"{name}:y": y, f"{name}:gy": gy, f"{name}:gx": gx})
+    npz("g11_solvers", **arrs)
+
+
+RECIPES = {"g1": g1, "g2_g4": g2_g4, "g5": g5, "g6": g6, "g7": g7, "g8": g8, "g9": g9, "g10": g10, "g11": g11}
+
 if __name__ == "__main__":
-    g1()
-    g2_g4()
-    g5()
-    g6()
-    g7()
-    g8()
-    g9()
-    g10()
+    # `python tools/make_goldens.py g11` regenerates one file; no argument: all of them
+    for key in (sys.argv[1:] or RECIPES):
+        RECIPES[key]()

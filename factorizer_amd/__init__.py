@@ -11,7 +11,7 @@ from .nmf import (NMF, SVD, BCDSolver, Compose, CoordinateDescent, FastMultiplic
                   LeastSquares, MatrixFactorization, MultiplicativeUpdate, NNDSVDInit, ProjectedGradient,
                   RandomInit, SemiMultiplicativeUpdate, SVDInit, WeightedMultiplicativeUpdate, relative_error)
 from .layers import MLP, LayerNorm, Linear, PosEmbed, PositionalEmbedding
-from .convs import Conv3d, ConvTranspose3d
+from .convs import Conv2d, Conv3d, ConvTranspose2d, ConvTranspose3d
 from .blocks import FactMixer, FactorizerBlock, FactorizerStage
 from .losses import DiceCELoss, dice_bce_loss, dice_ce_loss
 from .training import FlatAdamW, WarmupCosineSchedule, load_checkpoint, load_checkpoints

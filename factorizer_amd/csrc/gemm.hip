@@ -2618,7 +2618,10 @@ enum { PRO_NONE = 0, PRO_LN = 1, PRO_GELU = 2, PRO_BMUL = 3 };
 template <int MB, int NACC, int LOADER, int EPI, int PRO, int KS = 1, typename AT = float>
 __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate operand in the ring */) ? 1 : 2)) void gemm_stream_kernel(GemmArgsT<AT> p) {
   constexpr int TN = 32 * NACC;
-  constexpr int NL = (LOADER == LOAD_S2D) ? 4 : NACC;  // floats fetched per load step
+  // the 2-D loaders (LOAD_S2D_2D, LOAD_K3_2D) share the column decode, ring and MFMA order of their 3-D forms
+  constexpr bool S2DL = LOADER == LOAD_S2D || LOADER == LOAD_S2D_2D;
+  constexpr bool K3L = LOADER == LOAD_K3 || LOADER == LOAD_K3_2D;
+  constexpr int NL = S2DL ? 4 : NACC;  // floats fetched per load step
   // operand prefetch depth (load steps): narrow tiles are latency-bound (L2 round trip ≈ 500-900
   // cycles vs 64·NACC MFMA cycles per step), so they keep more loads in flight
   constexpr int kPF = (NL == 4) ? 8 : 16;
@@ -2679,7 +2682,7 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
   int64_t col_off;
   bool col_ok;
   int kw0 = 0, kh0 = 0, kd0 = 0;
-  if (LOADER == LOAD_S2D) {
+  if (S2DL) {
     const int64_t n = n0 + 2 * j;  // coarse voxel pair (wo even)
     col_ok = n < p.Ncol;
     const int64_t nn = col_ok ? n : 0;
@@ -2691,7 +2694,7 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
   } else {
     col_off = n0 + NACC * j;
     col_ok = col_off < p.Ncol;
-    if (LOADER == LOAD_K3) {
+    if (K3L) {
       const int64_t nn = col_ok ? col_off : 0;
       kw0 = (int)(nn % p.Wi);
       kh0 = (int)((nn / p.Wi) % p.Hi);
@@ -2703,6 +2706,15 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
   auto fetch = [&](int s, float (&v)[NR]) {
     if constexpr (LOADER == LOAD_PLAIN) {
       fetch_plain_raw<NL, PRO == PRO_BMUL>(p, b, 2 * s + h, col_off, col_ok, v);
+    } else if constexpr (LOADER == LOAD_S2D_2D) {
+      // rows k = (c, th, tw): load step s = (channel pair, th); 4 fine pixels = (tw 0, 1) of two coarse pixels
+      const int c = 2 * (s >> 1) + h;
+      const bool ok = col_ok && c < p.Cin;
+      const int cc = c < p.Cin ? c : p.Cin - 1;
+      const int64_t off = (col_ok ? col_off : 0) + (int64_t)(s & 1) * p.Wi;
+      vload<NL>(p.x[0] + ((int64_t)b * p.Cin + cc) * p.Vin + off, v);
+#pragma unroll
+      for (int e = 0; e < NL; ++e) v[e] = ok ? v[e] : 0.f;
     } else if constexpr (LOADER == LOAD_S2D) {
       const int c = 2 * (s >> 2) + h;
       const bool ok = col_ok && c < p.Cin;
@@ -2712,10 +2724,12 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
 #pragma unroll
       for (int e = 0; e < NL; ++e) v[e] = ok ? v[e] : 0.f;
     } else {
-      // LOAD_K3 (NL == 4): taps of the 3x3x3 stencil, zero padding — clamped addresses + selects
-      const int c = 2 * (s / 27) + h;
-      const int tap = s % 27;
-      const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
+      // LOAD_K3 (NL == 4): taps of the 3x3x3 stencil, zero padding — clamped addresses + selects.
+      // LOAD_K3_2D: the 3x3 stencil on a depth-1 grid (Di = 1): taps (kh, kw), the depth tap fixed at the centre
+      constexpr int NT = (LOADER == LOAD_K3_2D) ? 9 : 27;
+      const int c = 2 * (s / NT) + h;
+      const int tap = s % NT;
+      const int kd = (NT == 9) ? 1 : tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
       const int zd = kd0 + kd - 1, zh = kh0 + kh - 1;
       const bool ok = col_ok && c < p.Cin && zd >= 0 && zd < p.Di && zh >= 0 && zh < p.Hi;
       const int cc = c < p.Cin ? c : p.Cin - 1;
@@ -2749,7 +2763,7 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
 #pragma unroll
   for (int e = 0; e < NACC; ++e) s1[e] = s2[e] = shift[e] = 0.f;
 
-  const int nload = (LOADER == LOAD_S2D) ? nA / 2 : nA;
+  const int nload = S2DL ? nA / 2 : nA;
   float ring[kPF][NR];
   // unconditional, clamped prefetch: a load inside a branch costs an s_waitcnt vmcnt(0)
 #pragma unroll
@@ -2770,7 +2784,7 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
     }
   }
 
-  constexpr int kGroup = kPF * ((LOADER == LOAD_S2D) ? 2 : 1);
+  constexpr int kGroup = kPF * (S2DL ? 2 : 1);
   static_assert(CH % (KS * kGroup) == 0, "chunk must hold whole rounds of (K-split) prefetch groups");
   // steps are processed in groups of kPF*ASTEP with NO per-step guard (a guard turns every K-step into
   // its own basic block: ds_read → s_waitcnt lgkmcnt(0) → MFMA, fully serialised); the tail of the
@@ -2809,7 +2823,7 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
     const bool more = a0 + CH < nA;
     if (DB && more) load_chunk(a0 + CH, min(CH, nA - a0 - CH));  // in flight during the MFMAs below
     const float* Ab = As + cbuf * kBufFloats;
-    constexpr int ASTEP = (LOADER == LOAD_S2D) ? 2 : 1;
+    constexpr int ASTEP = S2DL ? 2 : 1;
     // kAChunk is a multiple of kPF*ASTEP, so the ring slot of a step is static after unrolling
     for (int al = (KS > 1 ? wave * kPF * ASTEP : 0); al < an_pad; al += KS * kPF * ASTEP) {
 #pragma unroll
@@ -2820,7 +2834,7 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
 #pragma unroll
         for (int e = 0; e < NR; ++e) cur[e] = ring[u][e];
         {
-          if (LOADER == LOAD_S2D) {
+          if (S2DL) {
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
               const float av0 = Ab[(ali * MB + mb) * 64 + lane];        // tw = 0
@@ -2957,7 +2971,7 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
     }
   }
   if (!col_ok) return;
-  const int64_t ncol = (LOADER == LOAD_S2D) ? n0 + 2 * j : col_off;
+  const int64_t ncol = S2DL ? n0 + 2 * j : col_off;
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
     if (PRO == PRO_LN) {
@@ -2970,7 +2984,7 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
         for (int q = 0; q < NACC; ++q) acc[mb][q][r] = rstd[q] * (acc[mb][q][r] - mu_d[q] * sw);
       }
     }
-    store_block<NACC, EPI, LOADER == LOAD_S2D>(p, acc[mb], b, m0 + mb * 32, ncol, h,
+    store_block<NACC, EPI, S2DL>(p, acc[mb], b, m0 + mb * 32, ncol, h,
                                                 PRO == PRO_LN ? tW + mb * 32 : nullptr);
   }
 }
@@ -3016,8 +3030,24 @@ extern "C" int fz_gemm_bx_enable(int on) {
 template <typename AT>
 static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
   if (!d->x[0] || !d->w || !d->y) return fail(FZ_E_ARG, "fz_gemm: null pointer");
-  if (d->loader < LOAD_PLAIN || d->loader > LOAD_K3) return fail(FZ_E_ARG, "fz_gemm: bad loader");
-  if (d->epilogue < EPI_PLAIN || d->epilogue > EPI_LNBWD) return fail(FZ_E_ARG, "fz_gemm: bad epilogue");
+  if (d->loader < LOAD_PLAIN || d->loader > LOAD_K3_2D) return fail(FZ_E_ARG, "fz_gemm: bad loader");
+  if (d->epilogue < EPI_PLAIN || d->epilogue > EPI_D2S_2D) return fail(FZ_E_ARG, "fz_gemm: bad epilogue");
+  {
+    // the 2-D forms (Conv2d k2s2 / k3p1, ConvTranspose2d k2s2): one loader OR one epilogue, no prologue, one source
+    const bool l2 = d->loader == LOAD_S2D_2D || d->loader == LOAD_K3_2D, e2 = d->epilogue == EPI_D2S_2D;
+    if ((l2 || e2) && ((l2 && d->epilogue != EPI_PLAIN) || (e2 && d->loader != LOAD_PLAIN) || d->ln || d->bact || d->bmul ||
+                       d->emul || d->eact || d->nsrc != 1 || d->src_mode != 0 || d->stats_out))
+      return fail(FZ_E_ARG, "fz_gemm: a 2-D loader / epilogue takes one source, a plain partner and no prologue / activation");
+    if (d->loader == LOAD_S2D_2D && (d->K != 4 * d->Cin || (d->Wo & 1) || d->Ho < 1 || d->Wo < 1 || d->Hi != 2 * d->Ho ||
+                                     d->Wi != 2 * d->Wo || d->Ncol != (int64_t)d->Ho * d->Wo || d->Vin != (int64_t)d->Hi * d->Wi ||
+                                     d->res))
+      return fail(FZ_E_SHAPE, "fz_gemm: 2-D space-to-depth needs K = 4*Cin, (Hi, Wi) = 2*(Ho, Wo), even Wo, Ncol = Ho*Wo");
+    if (d->loader == LOAD_K3_2D && (d->K != 9 * d->Cin || (d->Cin & 1) || d->Hi < 1 || d->Wi < 4 || (d->Wi & 3) ||
+                                    d->Ncol != (int64_t)d->Hi * d->Wi || d->Vin != d->Ncol || d->res))
+      return fail(FZ_E_SHAPE, "fz_gemm: 2-D 3x3 loader needs K = 9*Cin, even Cin, W % 4 == 0, Ncol = Vin = H*W");
+    if (e2 && (d->M % 4 != 0 || d->Ho < 1 || d->Wo < 1 || d->Ncol != (int64_t)d->Ho * d->Wo || d->Vin != d->Ncol || (d->Ncol & 3)))
+      return fail(FZ_E_SHAPE, "fz_gemm: 2-D depth-to-space needs M = 4*O, Ncol = Vin = Ho*Wo, a multiple of 4");
+  }
   const bool lnb64 = d->epilogue == EPI_LNBWD && d->M == 64 && d->K == 64 && d->nsrc == 1 && !d->bmul;
   if (d->epilogue == EPI_LNBWD && ((!lnb64 && (d->M != 32 || (d->K != 32 && d->K != 64))) || d->loader != LOAD_PLAIN || !d->lnb_x || !d->lnb_stats ||
                                    !d->lnb_g || !d->lnb_part || d->bias || d->res || d->emul || d->eact || d->ln))
@@ -3047,6 +3077,7 @@ static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
   a.bias = d->bias; a.ln = d->ln; a.ln_g = d->ln_g; a.ln_b = d->ln_b; a.ln_eps = d->ln_eps;
   a.stats_out = d->stats_out; a.bact = d->bact; a.eact = d->eact; a.res = (const AT*)d->res; a.emul = (const AT*)d->emul;
   a.emul_kind = d->emul_kind; a.y = (AT*)d->y; a.Ncol = d->Ncol; a.Ho = d->Ho; a.Wo = d->Wo; a.B = d->B;
+  if (d->loader == LOAD_S2D_2D || d->loader == LOAD_K3_2D) a.Di = 1;   // the kernels' depth bound of a 2-D grid
   a.dbg = 0; a.tile_map = 1;
   a.ygroups = 0; a.xtiles = 0; a.tune = d->tune;
   a.lnb_x = (const AT*)d->lnb_x; a.lnb_stats = d->lnb_stats; a.lnb_g = d->lnb_g; a.lnb_gadd = (const AT*)d->lnb_gadd; a.lnb_part = d->lnb_part;
@@ -3119,7 +3150,7 @@ static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
   // kernel stays ahead (round-1/2 probe `gemm_probe9`)
   const bool stream_small = mblocks == 1 && d->K >= 16 && d->K <= 32 && !d->res && !d->bmul && !d->emul &&
                             d->epilogue == EPI_PLAIN && d->bact == 0;
-  if (d->loader == LOAD_PLAIN && d->K <= res_maxk && !stream_small) {
+  if (d->loader == LOAD_PLAIN && d->K <= res_maxk && !stream_small && d->epilogue != EPI_D2S_2D) {
     const int nA = (d->K + 1) / 2;
     int RB = mblocks < 8 ? mblocks : 8;
     while ((size_t)(nA * RB * 64 + 32 * RB) * sizeof(float) > 65536) --RB;
@@ -3164,7 +3195,7 @@ static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
   // column tile that still gives >= 256 workgroups (one per CU); two row blocks per workgroup only
   // when that still leaves >= 512 workgroups
   int nacc = 4, MBsel = mblocks >= 2 ? 2 : 1;
-  if (d->loader == LOAD_S2D) { nacc = 2; MBsel = 1; }
+  if (d->loader == LOAD_S2D || d->loader == LOAD_S2D_2D) { nacc = 2; MBsel = 1; }
   else {
     const bool narrow_ok = d->loader == LOAD_PLAIN && d->epilogue == EPI_PLAIN;
     auto wgs = [&](int na, int mb) {
@@ -3188,7 +3219,7 @@ static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
   {
     const int64_t wg1 = ((d->Ncol + TN * 4 - 1) / (TN * 4)) * d->B * ((mblocks + MBsel - 1) / MBsel);
     const bool shape_ok = MBsel == 1 && ((d->loader == LOAD_PLAIN && d->epilogue == EPI_PLAIN && nacc <= 2) ||
-                                         d->loader == LOAD_S2D);
+                                         d->loader == LOAD_S2D || d->loader == LOAD_S2D_2D);
     if (shape_ok && wg1 < 256 && d->K >= 256) ks = 4;
   }
   const int WT = ks > 1 ? 1 : 4;
@@ -3209,6 +3240,9 @@ static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
   if ((d->ln != 0) + (d->bact != 0) + (d->bmul != nullptr) > 1)
     return fail(FZ_E_UNSUPPORTED, "fz_gemm: at most one input prologue (LayerNorm / GELU / gate)");
   if (d->loader == LOAD_S2D) { if (ks == 4) FZ_STRK(1, 2, LOAD_S2D, EPI_PLAIN, PRO_NONE); else FZ_STR(1, 2, LOAD_S2D, EPI_PLAIN, PRO_NONE); }
+  else if (d->loader == LOAD_S2D_2D) { if (ks == 4) FZ_STRK(1, 2, LOAD_S2D_2D, EPI_PLAIN, PRO_NONE); else FZ_STR(1, 2, LOAD_S2D_2D, EPI_PLAIN, PRO_NONE); }
+  else if (d->loader == LOAD_K3_2D) { if (MBsel == 2) FZ_STR(2, 4, LOAD_K3_2D, EPI_PLAIN, PRO_NONE); else FZ_STR(1, 4, LOAD_K3_2D, EPI_PLAIN, PRO_NONE); }
+  else if (d->epilogue == EPI_D2S_2D) { if (MBsel == 2) FZ_STR(2, 4, LOAD_PLAIN, EPI_D2S_2D, PRO_NONE); else FZ_STR(1, 4, LOAD_PLAIN, EPI_D2S_2D, PRO_NONE); }
   else if (d->loader == LOAD_K3) { if (MBsel == 2) FZ_STR(2, 4, LOAD_K3, EPI_PLAIN, PRO_NONE); else FZ_STR(1, 4, LOAD_K3, EPI_PLAIN, PRO_NONE); }
   else if (d->epilogue == EPI_D2S) {
     if (pro != PRO_NONE) return fail(FZ_E_UNSUPPORTED, "fz_gemm: prologue with depth-to-space epilogue");

@@ -9,8 +9,8 @@ namespace fz {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-enum { LOAD_PLAIN = 0, LOAD_S2D = 1, LOAD_K3 = 2 };
-enum { EPI_PLAIN = 0, EPI_D2S = 1, EPI_LNBWD = 2 };
+enum { LOAD_PLAIN = 0, LOAD_S2D = 1, LOAD_K3 = 2, LOAD_S2D_2D = 3, LOAD_K3_2D = 4 };
+enum { EPI_PLAIN = 0, EPI_D2S = 1, EPI_LNBWD = 2, EPI_D2S_2D = 3 };
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
 
 // AT = storage type of the activation tensors (float or bf16, fz_common.h); everything else is fp32
@@ -22,11 +22,11 @@ struct GemmArgsT {
   int c0;
   int Cin;             // input channels
   int64_t Vin;         // voxels per sample of the input tensor(s)
-  int Di, Hi, Wi;      // input D, H, W (LOAD_S2D: fine tensor; LOAD_K3: the grid)
+  int Di, Hi, Wi;      // input D, H, W (LOAD_S2D: fine tensor; LOAD_K3: the grid; 2-D loaders: Di = 1)
   const float* w;      // weights
   int w_t, ldw;        // A[m][k] = w_t ? w[k*ldw + m] : w[m*ldw + k]
   int M, K;            // output rows, reduction length
-  const float* bias;   // [M] (EPI_PLAIN) or [M/8] (EPI_D2S), may be null
+  const float* bias;   // [M] (EPI_PLAIN), [M/8] (EPI_D2S) or [M/4] (EPI_D2S_2D), may be null
   int ln;              // LayerNorm prologue over the Cin channels
   const float* ln_g;
   const float* ln_b;
@@ -98,6 +98,8 @@ template <int LOADER>
 __device__ __forceinline__ int a_k(int a, int h) {
   if (LOADER == LOAD_S2D) return (2 * (a >> 3) + h) * 8 + (a & 7);
   if (LOADER == LOAD_K3) return (2 * (a / 27) + h) * 27 + (a % 27);
+  if (LOADER == LOAD_S2D_2D) return (2 * (a >> 2) + h) * 4 + (a & 3);
+  if (LOADER == LOAD_K3_2D) return (2 * (a / 9) + h) * 9 + (a % 9);
   return 2 * a + h;
 }
 
@@ -196,6 +198,52 @@ __device__ __forceinline__ void store_block(const GemmArgsT<AT>& p, const f32x16
         for (int q = 0; q < NACC; ++q) v[q] += e[q];
       }
       vstore<NACC>(p.y + o, v);
+    }
+  } else if (EPI == EPI_D2S_2D) {
+    // 2-D: rows are (o, tap): m = o*4 + th*2 + tw ; inside a 32-row block o_local = 2*(r>>2) + h,
+    // th = (r>>1)&1, tw = r&1.  Columns ncol..ncol+3 are coarse pixels (ho, wo); the fine tensor
+    // gets 8 consecutive pixels (tw pairs) per (o, th).
+    const int Wf = 2 * p.Wo;
+    const int64_t Vf = 4 * p.Ncol;
+    const int Mo = p.M >> 2;
+#pragma unroll
+    for (int rp = 0; rp < 8; ++rp) {
+      const int r0 = 2 * rp;
+      const int o = (mrow0 >> 2) + 2 * (r0 >> 2) + h;
+      if (o >= Mo) continue;
+      const int th = (r0 >> 1) & 1;
+      const float bs = p.bias ? p.bias[o] : 0.f;
+      const int64_t obase = ((int64_t)b * Mo + o) * Vf;
+      AT* ybase = p.y + obase;
+      if (NACC == 4 && (p.Wo & 3) == 0) {
+        const int wo = (int)(ncol % p.Wo);
+        const int64_t ho = ncol / p.Wo;
+        const int64_t fo = (2 * ho + th) * Wf + 2 * wo;
+        float o8[8] = {acc[0][r0] + bs, acc[0][r0 + 1] + bs, acc[1 % NACC][r0] + bs, acc[1 % NACC][r0 + 1] + bs,
+                       acc[2 % NACC][r0] + bs, acc[2 % NACC][r0 + 1] + bs, acc[3 % NACC][r0] + bs, acc[3 % NACC][r0 + 1] + bs};
+        if (p.res) {
+          float r8[8];
+          vload<8>(p.res + obase + fo, r8);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) o8[i] += r8[i];
+        }
+        vstore<8>(ybase + fo, o8);
+      } else {
+#pragma unroll
+        for (int q = 0; q < NACC; ++q) {
+          const int64_t nq = ncol + q;
+          const int wo = (int)(nq % p.Wo);
+          const int64_t ho = nq / p.Wo;
+          const int64_t fo = (2 * ho + th) * Wf + 2 * wo;
+          float v2[2] = {acc[q][r0] + bs, acc[q][r0 + 1] + bs};
+          if (p.res) {
+            float r2[2];
+            vload<2>(p.res + obase + fo, r2);
+            v2[0] += r2[0]; v2[1] += r2[1];
+          }
+          vstore<2>(ybase + fo, v2);
+        }
+      }
     }
   } else {
     // rows are (o, tap): m = o*8 + td*4 + th*2 + tw ; inside a 32-row block td = h,

@@ -45,7 +45,7 @@ __device__ __forceinline__ void split_bf16x8(const float (&x)[8], bf16x8& hi, bf
   }
 }
 
-enum { QL_PLAIN = 0, QL_S2D = 1, QL_K3 = 2 };
+enum { QL_PLAIN = 0, QL_S2D = 1, QL_K3 = 2, QL_S2D_2D = 3, QL_K3_2D = 4 };
 
 // AT = storage type of the activation tensors p, pmul, q (float or bf16); everything else is fp32
 template <typename AT>
@@ -195,8 +195,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgsT<AT> a) {
       }
     }
     commit_tiles(t);
-    if (QL == QL_S2D) {
-      // rows k = (ci, td, th, tw); one 16-byte load gives (tw0,tw1) of two coarse voxels
+    if (QL == QL_S2D || QL == QL_S2D_2D) {
+      // rows k = (ci, td, th, tw) (2-D: (ci, th, tw), td = 0 on a depth-1 grid); one 16-byte load gives (tw0,tw1) of two
+      // coarse voxels
 #pragma unroll
       for (int i = 0; i < (QR / 2) * 16 / 64; ++i) {
         const int idx = lane + 64 * i;
@@ -206,7 +207,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgsT<AT> a) {
         const bool ok = k < a.K && n < a.N;
         const int kc = k < a.K ? k : 0;
         const int64_t nn = n < a.N ? n : 0;
-        const int ci = kc >> 3, td = (kc >> 2) & 1, th = (kc >> 1) & 1;
+        constexpr int TS = (QL == QL_S2D_2D) ? 2 : 3;   // log2(taps per input channel)
+        const int ci = kc >> TS, td = (QL == QL_S2D_2D) ? 0 : (kc >> 2) & 1, th = (kc >> 1) & 1;
         const int wo = (int)(nn % a.Wo);
         const int64_t t2 = nn / a.Wo;
         const int ho = (int)(t2 % a.Ho);
@@ -217,8 +219,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgsT<AT> a) {
         float* d1 = d0 + kStride;
         d0[0] = ok ? v.x : 0.f; d1[0] = ok ? v.y : 0.f; d0[1] = ok ? v.z : 0.f; d1[1] = ok ? v.w : 0.f;
       }
-    } else if (QL == QL_K3) {
-      // QL_K3: rows k = ci*27 + (kd*9 + kh*3 + kw); zero padding 1.  Lane = (column, row parity):
+    } else if (QL == QL_K3 || QL == QL_K3_2D) {
+      // QL_K3: rows k = ci*27 + (kd*9 + kh*3 + kw); zero padding 1 (QL_K3_2D: ci*9 + (kh*3 + kw) on a depth-1 grid,
+      // the depth tap at the centre).  Lane = (column, row parity):
       // the voxel coordinates are decoded once per tile, the tap once per (uniform) row.
       const int col = lane & 31;
       const int64_t n = n0 + col;
@@ -231,8 +234,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgsT<AT> a) {
       for (int r = lane >> 5; r < QR; r += 2) {
         const int k = k0 + r;
         const int kc = k < a.K ? k : 0;
-        const int ci = kc / 27, tap = kc % 27;
-        const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
+        constexpr int NT = (QL == QL_K3_2D) ? 9 : 27;
+        const int ci = kc / NT, tap = kc % NT;
+        const int kd = (NT == 9) ? 1 : tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
         const int zd = dz + kd - 1, zh = hh + kh - 1, zw = w + kw - 1;
         const bool ok = nok && k < a.K && zd >= 0 && zd < a.D && zh >= 0 && zh < a.H && zw >= 0 && zw < a.W;
         const int zdc = min(max(zd, 0), a.D - 1), zhc = min(max(zh, 0), a.H - 1), zwc = min(max(zw, 0), a.W - 1);
@@ -492,7 +496,14 @@ struct WgradPlan {
 template <typename AT>
 static int wgrad_plan(const fz_wgrad_desc* d, void* workspace, WgradPlan<AT>& pl) {
   if (!d->p || !d->q[0] || !d->gw) return fail(FZ_E_ARG, "fz_wgrad: null pointer");
-  if (d->loader < 0 || d->loader > 2) return fail(FZ_E_ARG, "fz_wgrad: bad loader");
+  if (d->loader < 0 || d->loader > QL_K3_2D) return fail(FZ_E_ARG, "fz_wgrad: bad loader");
+  if ((d->loader == QL_S2D_2D || d->loader == QL_K3_2D) && (d->nsrc != 1 || d->src_mode != 0 || d->stats || d->qact))
+    return fail(FZ_E_ARG, "fz_wgrad: a 2-D loader takes one source and no Q prologue");
+  if (d->loader == QL_S2D_2D && (d->K != 4 * d->Cin || (d->Wo & 1) || d->Ho < 1 || d->Wo < 1 || d->H != 2 * d->Ho ||
+                                 d->W != 2 * d->Wo || d->N != (int64_t)d->Ho * d->Wo || d->Vq != (int64_t)d->H * d->W))
+    return fail(FZ_E_SHAPE, "fz_wgrad: 2-D s2d shape (K = 4*Cin, (H, W) = 2*(Ho, Wo), even Wo, N = Ho*Wo)");
+  if (d->loader == QL_K3_2D && (d->K != 9 * d->Cin || d->H < 1 || d->W < 1 || d->N != (int64_t)d->H * d->W || d->Vq != d->N))
+    return fail(FZ_E_SHAPE, "fz_wgrad: 2-D k3 shape (K = 9*Cin, N = Vq = H*W)");
   if (d->N % 4 != 0) return fail(FZ_E_UNSUPPORTED, "fz_wgrad: column count must be a multiple of 4");
   if (d->loader == QL_S2D && ((d->Wo & 1) || d->K != 8 * d->Cin)) return fail(FZ_E_SHAPE, "fz_wgrad: s2d shape");
   if (d->loader == QL_K3 && d->K != 27 * d->Cin) return fail(FZ_E_SHAPE, "fz_wgrad: k3 shape");
@@ -509,6 +520,7 @@ static int wgrad_plan(const fz_wgrad_desc* d, void* workspace, WgradPlan<AT>& pl
   for (int i = 0; i < 4; ++i) a.q[i] = (const AT*)d->q[i];
   a.nsrc = d->nsrc; a.src_mode = d->src_mode; a.c0 = d->c0 > 0 ? d->c0 : d->Cin; a.Cin = d->Cin; a.K = d->K;
   a.Vq = d->Vq; a.D = d->D; a.H = d->H; a.W = d->W; a.N = d->N; a.Ho = d->Ho; a.Wo = d->Wo;
+  if (d->loader == QL_S2D_2D || d->loader == QL_K3_2D) a.D = 1;   // the k3 loader's depth bound of a 2-D grid
   a.stats = d->stats; a.qact = d->qact; a.B = d->B; a.tiles_per_chunk = tpc;
   a.part = (float*)workspace;
   a.part_bias = a.part + (int64_t)pl.nchunk * d->M * d->K;
@@ -568,6 +580,8 @@ static int wgrad_main_launch(const fz_wgrad_desc* d, const WgradPlan<AT>& pl, hi
     else FZ_WGF_SHAPES(QP_NONE);
   } else if (d->loader == QL_PLAIN) FZ_WG_SHAPES(QL_PLAIN);
   else if (d->loader == QL_S2D) FZ_WG_SHAPES(QL_S2D);
+  else if (d->loader == QL_S2D_2D) FZ_WG_SHAPES(QL_S2D_2D);
+  else if (d->loader == QL_K3_2D) FZ_WG_SHAPES(QL_K3_2D);
   else FZ_WG_SHAPES(QL_K3);
   FZ_LAUNCH_CHECK();
   return FZ_OK;

@@ -290,7 +290,7 @@ class Deconver(UNet):
                  stem=None, downsample=None, upsample=None, head=None, num_deep_supr=False, **kwargs):
         stages = (len(encoder_depth) + len(decoder_depth)) * [DeconverStage]
         if stem is None:
-            conv = convs.Conv3d if spatial_dims == 3 else getattr(nn, f"Conv{spatial_dims}d")
+            conv = {3: convs.Conv3d, 2: convs.Conv2d}.get(spatial_dims) or getattr(nn, f"Conv{spatial_dims}d")
             stem = (conv, {"kernel_size": 3, "padding": 1, "bias": False})
         super().__init__(in_channels, out_channels, spatial_dims=spatial_dims, encoder_depth=encoder_depth,
                          encoder_width=encoder_width, strides=strides, decoder_depth=decoder_depth, stem=stem,

@@ -8,6 +8,7 @@ Each autograd Function below is one fused layer of the reference block:
   LinearFn        plain Linear                              linear.py:53-58
   CatLinearFn     Linear(cat([x1, x2], 1)) without the cat  unet.py:128 + factorizer.py:116
   ConvK2S2Fn / TConvK2S2Fn / ConvK3Fn / ConvK1            unet.py:53,123,231,253
+  ConvK2S2Fn2d / SkipConvK2S2Fn2d / TConvK2S2Fn2d / ConvK3Fn2d   the same layers of a 2-D U-shape
 """
 from __future__ import annotations
 
@@ -24,8 +25,10 @@ from . import gradbuf as _GB
 from . import functional as Fn
 
 ACT = {"none": 0, "relu": 1, "gelu": 2}
-LOAD_PLAIN, LOAD_S2D, LOAD_K3 = 0, 1, 2
-EPI_PLAIN, EPI_D2S = 0, 1
+LOAD_PLAIN, LOAD_S2D, LOAD_K3, LOAD_S2D_2D, LOAD_K3_2D = 0, 1, 2, 3, 4
+EPI_PLAIN, EPI_D2S, EPI_D2S_2D = 0, 1, 3
+QL_S2D_2D, QL_K3_2D = 3, 4
+_D2S_FINE = {EPI_D2S: 8, EPI_D2S_2D: 4}   # fine voxels per coarse column of a depth-to-space epilogue
 
 
 def _p(t):
@@ -65,7 +68,7 @@ def _gemm(xs, w, y, *, B, Cin, Vin, M, K, Ncol, w_t=False, ldw=None, bias=None, 
     with torch.cuda.device(x0.device):
         rc = Fn._timed(f"{name}_{Cin}->{M}", nbytes,
                        lambda: N.lib().fz_gemm(ctypes.byref(d), N.stream_ptr(x0)),
-                       cols=B * max(Vin, Ncol * (8 if epilogue == EPI_D2S else 1)), flops=2 * B * Ncol * M * K)
+                       cols=B * max(Vin, Ncol * _D2S_FINE.get(epilogue, 1)), flops=2 * B * Ncol * M * K)
     N.check(rc, "fz_gemm")
     return y
 
@@ -1052,6 +1055,159 @@ class ConvK3Fn(torch.autograd.Function):
             _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=27 * C, Vq=V, Ncols=V, gbias=gb, loader=LOAD_K3, D=D, H=H, W=W,
                    name="wgrad_conv_k3")
         return (gx, gw, (gb if ctx.has_bias else None), None)[:len(ctx.needs_input_grad)]   # (one per argument actually passed)
+
+
+
+# ---- the same convolutions of a 2-D U-shape (Conv2d / ConvTranspose2d; convs.Conv2d, convs.ConvTranspose2d) -------------
+# Tap orders (weights are used in place, no packing pass): k2s2 rows / columns k = (c, th, tw) = c*4 + th*2 + tw, i.e. the
+# row-major flattening of Conv2d's (O, C, 2, 2) weight and ConvTranspose2d's (C, O, 2, 2) weight; k3p1 k = (c, kh, kw) =
+# c*9 + kh*3 + kw, the flattening of (O, C, 3, 3).  DESIGN.md §3 "2-D tap geometries".
+class ConvK2S2Fn2d(torch.autograd.Function):
+    """Conv2d(kernel 2, stride 2): 2-D space-to-depth gather fused into the GEMM's operand loads (LOAD_S2D_2D)."""
+
+    @staticmethod
+    @N.capture_products
+    def forward(ctx, x, w, b):
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        O = w.shape[0]
+        Ho, Wo = H // 2, W // 2
+        y = torch.empty((B, O, Ho, Wo), dtype=x.dtype, device=x.device)
+        _gemm([x], w, y, B=B, Cin=C, Vin=H * W, M=O, K=4 * C, Ncol=Ho * Wo, bias=b, loader=LOAD_S2D_2D,
+              Di=1, Hi=H, Wi=W, Ho=Ho, Wo=Wo, name="conv2d_k2s2")
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy, g_skip=None):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        B, C, H, W = x.shape
+        O = w.shape[0]
+        Ho, Wo = H // 2, W // 2
+        Vc = Ho * Wo
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            if g_skip is not None:
+                g_skip = g_skip.contiguous()
+            # rows (ci, th, tw), reduction over o:  A[m][k] = w[k*(4C) + m]; the skip gradient is the epilogue's residual
+            _gemm([gy], w, gx, B=B, Cin=O, Vin=Vc, M=4 * C, K=O, Ncol=Vc, w_t=True, ldw=4 * C,
+                  epilogue=EPI_D2S_2D, Ho=Ho, Wo=Wo, res=g_skip, name="conv2d_k2s2_dgrad")
+        gw = _GB.out_like(w)
+        gb = torch.empty(O, dtype=torch.float32, device=x.device)
+        _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=4 * C, Vq=H * W, Ncols=Vc, gbias=gb, loader=QL_S2D_2D,
+               D=1, H=H, W=W, Ho=Ho, Wo=Wo, name="wgrad_conv2d_k2s2")
+        return gx, gw, (gb if ctx.has_bias else None)
+
+
+class SkipConvK2S2Fn2d(torch.autograd.Function):
+    """(x, Conv2d(k=2, s=2)(x)) as ONE node (SkipConvK2S2Fn in 2-D)."""
+
+    @staticmethod
+    @N.capture_products
+    def forward(ctx, x, w, b):
+        y = ConvK2S2Fn2d.forward(ctx, x, w, b)
+        return x.view_as(x), y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, g_skip, gy):
+        if gy is None:  # the down path took no part in the loss
+            return g_skip, None, None
+        return ConvK2S2Fn2d.backward(ctx, gy, g_skip=g_skip)
+
+
+class TConvK2S2Fn2d(torch.autograd.Function):
+    """ConvTranspose2d(kernel 2, stride 2): GEMM with (o, th, tw) rows + 2-D depth-to-space epilogue (EPI_D2S_2D)."""
+
+    @staticmethod
+    @N.capture_products
+    def forward(ctx, x, w, b):
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        O = w.shape[1]
+        y = torch.empty((B, O, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
+        V = H * W
+        _gemm([x], w, y, B=B, Cin=C, Vin=V, M=4 * O, K=C, Ncol=V, w_t=True, ldw=4 * O, bias=b,
+              epilogue=EPI_D2S_2D, Ho=H, Wo=W, name="tconv2d_k2s2")
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        B, C, H, W = x.shape
+        O = w.shape[1]
+        V = H * W
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            # GX[ci, coarse] = Σ_{o,th,tw} w[ci, o, th, tw] · GY[o, fine]: a 2-D k2s2 "conv" of gy with w as [C][4O]
+            _gemm([gy], w, gx, B=B, Cin=O, Vin=4 * V, M=C, K=4 * O, Ncol=V, loader=LOAD_S2D_2D,
+                  Di=1, Hi=2 * H, Wi=2 * W, Ho=H, Wo=W, name="tconv2d_k2s2_dgrad")
+        gw = _GB.out_like(w)
+        # GW[ci][(o,th,tw)] = Σ X[ci][n] · GY[o][fine(n,th,tw)]
+        _wgrad(x, [gy], gw, B=B, M=C, Cin=O, K=4 * O, Vq=4 * V, Ncols=V, loader=QL_S2D_2D, D=1, H=2 * H,
+               W=2 * W, Ho=H, Wo=W, name="wgrad_tconv2d_k2s2")
+        gb = None
+        if ctx.has_bias:
+            Vf = 4 * V
+            gb = torch.empty(O, dtype=torch.float32, device=x.device)
+            part = torch.empty(B * N.lib().fz_rowsum_chunks(Vf) * O, dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device), _finish_scope(part, gb):
+                rc = N.lib().fz_rowsum(gy.data_ptr(), part.data_ptr(), gb.data_ptr(), B, O, Vf, N.act_dtype(gy),
+                                       N.stream_ptr(x))
+            N.check(rc, "fz_rowsum")
+        return gx, gw, gb
+
+
+class ConvK3Fn2d(torch.autograd.Function):
+    """Conv2d(kernel 3, padding 1) — the stem of a 2-D U-shape: the 3x3 tap loader of the GEMM family (LOAD_K3_2D)."""
+
+    @staticmethod
+    @N.capture_products
+    def forward(ctx, x, w, b):
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        O = w.shape[0]
+        V = H * W
+        y = torch.empty((B, O, H, W), dtype=x.dtype, device=x.device)
+        _gemm([x], w, y, B=B, Cin=C, Vin=V, M=O, K=9 * C, Ncol=V, bias=b, loader=LOAD_K3_2D, Di=1, Hi=H, Wi=W,
+              name="conv2d_k3")
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        B, C, H, W = x.shape
+        O = w.shape[0]
+        V = H * W
+        gx = None
+        if ctx.needs_input_grad[0]:
+            # the adjoint is the same 3x3 correlation with the channel-transposed, spatially flipped filters
+            if O % 2 == 0:
+                wt = torch.flip(w, dims=(2, 3)).transpose(0, 1).contiguous()
+                gx = torch.empty_like(x)
+                _gemm([gy], wt, gx, B=B, Cin=O, Vin=V, M=C, K=9 * O, Ncol=V, loader=LOAD_K3_2D, Di=1, Hi=H, Wi=W,
+                      name="conv2d_k3_dgrad")
+            else:
+                _warn_composed("Conv2d(k=3) input gradient", x)
+                gx = torch.nn.grad.conv2d_input(x.shape, w, gy, padding=1)
+        gw = _GB.out_like(w)
+        gb = torch.empty(O, dtype=torch.float32, device=x.device)
+        _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=9 * C, Vq=V, Ncols=V, gbias=gb, loader=QL_K3_2D, D=1, H=H, W=W,
+               name="wgrad_conv2d_k3")
+        return gx, gw, (gb if ctx.has_bias else None)
 
 
 # ---- public dispatchers (device → native, CPU → composed ATen) ---------------------------------------

@@ -185,6 +185,8 @@ class UNet(nn.Module):
         n_enc, n_dec = len(encoder_depth), len(decoder_depth)
         if spatial_dims == 3:
             conv, tconv = convs.Conv3d, convs.ConvTranspose3d
+        elif spatial_dims == 2:
+            conv, tconv = convs.Conv2d, convs.ConvTranspose2d
         else:
             conv, tconv = getattr(nn, f"Conv{spatial_dims}d"), getattr(nn, f"ConvTranspose{spatial_dims}d")
         downsample = downsample or (conv, {"kernel_size": 2})
@@ -308,7 +310,7 @@ class Factorizer(UNet):
                  pos_embed=PositionalEmbedding, num_deep_supr=False, **kwargs):
         nd = len(spatial_size)
         if stem is None:
-            conv = convs.Conv3d if nd == 3 else getattr(nn, f"Conv{nd}d")
+            conv = {3: convs.Conv3d, 2: convs.Conv2d}.get(nd) or getattr(nn, f"Conv{nd}d")
             stem = (conv, {"kernel_size": 3, "padding": 1, "bias": False})
         plain = (FactorizerStage, kwargs)
         bottleneck = (FactorizerStage, {"pos_embed": pos_embed, **kwargs})

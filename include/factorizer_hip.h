@@ -216,7 +216,11 @@ int fz_act_add(void* dst, const void* src, int64_t n, int act_dtype, fz_stream_t
  *   Conv3d(k=2,s=2) downsample             unet.py:53   (loader = FZ_LOAD_S2D)
  *   ConvTranspose3d(k=2,s=2) upsample      unet.py:123  (epilogue = FZ_EPI_D2S)
  *   head Conv3d(k=1)                       unet.py:253
+ *   the same layers of a 2-D U-shape: Conv2d(k=2,s=2) (FZ_LOAD_S2D_2D), ConvTranspose2d(k=2,s=2) (FZ_EPI_D2S_2D), the
+ *   Conv2d(k=3,p=1) stem (FZ_LOAD_K3_2D)   unet.py:53,123, factorizer.py:145-149, deconver.py Deconver(spatial_dims=2)
  * and, with w_t (use the weight transposed), the input gradient of each of them.
+ * The 2-D forms take one source, no prologue / activation and the plain partner (loader or epilogue); Di is ignored.
+ * A wrong pairing returns FZ_E_ARG, inconsistent sizes (K, an odd Wo, grid / column counts) FZ_E_SHAPE.
  */
 #define FZ_LOAD_PLAIN 0 /* In[k][n] = x[b, k, n]                                             */
 #define FZ_LOAD_S2D 1   /* In[(c,td,th,tw)][coarse n] = x[b, c, 2d+td, 2h+th, 2w+tw]         */
@@ -224,6 +228,9 @@ int fz_act_add(void* dst, const void* src, int64_t n, int act_dtype, fz_stream_t
 #define FZ_EPI_PLAIN 0  /* y[b, m, n]                                                         */
 #define FZ_EPI_D2S 1    /* rows m = (o, td,th,tw): y[b, o, 2d+td, 2h+th, 2w+tw]               */
 #define FZ_EPI_LNBWD 2  /* M == 32: result = dL/d(LayerNorm out); y = LayerNorm backward of it  */
+#define FZ_LOAD_S2D_2D 3 /* In[(c,th,tw)][coarse n] = x[b, c, 2h+th, 2w+tw]; K = 4*Cin, Ncol = Ho*Wo, even Wo     */
+#define FZ_LOAD_K3_2D 4  /* In[(c,kh,kw)][n] = x[b, c, h+kh-1, w+kw-1], zero padded; K = 9*Cin, even Cin, W % 4 == 0 */
+#define FZ_EPI_D2S_2D 3  /* rows m = (o, th,tw): y[b, o, 2h+th, 2w+tw]; M = 4*O, bias [M/4], res = fine tensor    */
 #define FZ_ACT_NONE 0
 #define FZ_ACT_RELU 1
 #define FZ_ACT_GELU 2 /* exact erf GELU, layers/mlp.py:56 */
@@ -245,7 +252,7 @@ typedef struct fz_gemm_desc {
   const float* w;      /* weights                                                              */
   int w_t, ldw;        /* A[m][k] = w_t ? w[k*ldw + m] : w[m*ldw + k]                          */
   int M, K;            /* output rows, reduction length (even)                                 */
-  const float* bias;   /* [M] (plain) / [M/8] (d2s) or NULL                                    */
+  const float* bias;   /* [M] (plain) / [M/8] (d2s) / [M/4] (2-D d2s) or NULL                  */
   int ln;              /* LayerNorm prologue over Cin                                          */
   const float* ln_g;
   const float* ln_b;
@@ -463,6 +470,8 @@ int fz_mlp_chain_drop(const fz_mlp_desc* desc, const fz_mlp_dropout* drop, fz_st
 #define FZ_QL_PLAIN 0 /* Q[k][n] = in[b,k,n]                                     */
 #define FZ_QL_S2D 1   /* Q[(c,td,th,tw)][coarse n] = in[b,c,2d+td,2h+th,2w+tw]   */
 #define FZ_QL_K3 2    /* Q[(c,kd,kh,kw)][n] = in[b,c,d+kd-1,h+kh-1,w+kw-1] (zero pad) */
+#define FZ_QL_S2D_2D 3 /* Q[(c,th,tw)][coarse n] = in[b,c,2h+th,2w+tw]: K = 4*Cin, N = Ho*Wo, even Wo */
+#define FZ_QL_K3_2D 4  /* Q[(c,kh,kw)][n] = in[b,c,h+kh-1,w+kw-1] (zero pad): K = 9*Cin, N = H*W    */
 
 typedef struct fz_wgrad_desc {
   const void* p;      /* activation (B, M, N) output-side gradient                                    */
@@ -472,7 +481,7 @@ typedef struct fz_wgrad_desc {
   const void* q[4];   /* activation: input sources                                                 */
   int nsrc, src_mode, c0;
   int Cin;            /* input channels                                                      */
-  int K;              /* Q rows: Cin / 8*Cin / 27*Cin                                        */
+  int K;              /* Q rows: Cin / 8*Cin / 27*Cin (2-D: 4*Cin / 9*Cin)                   */
   int64_t Vq;         /* voxels per sample of the input                                      */
   int D, H, W;        /* input grid (s2d: fine grid; k3)                                     */
   int64_t N;          /* reduction columns per sample                                        */

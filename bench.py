@@ -1,6 +1,6 @@
 """bench.py — headline benchmark of the Factorizer hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,10 +9,15 @@ Metric (BASELINE.json): volumes/sec, forward+backward(+AdamW) of the README Swin
 batch 2, data-parallel over N GPUs with one flat-bucket RCCL all-reduce per step
 (BASELINE.json configs[3]; weak scaling).  Synthetic inputs, random-init weights, fp32.
 
-One JSON line is printed by rank 0.  `roofline` describes the dominant native kernel of the
-timed region (HIP events on the launch stream, algorithmic bytes of SURVEY.md §8d);
-`cpu_baseline` is the CPU oracle (oracle/cpu_ref.py, a port of the reference's CPU path) timed
-on this host on a bounded sample (rank 0, N=1 only).
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints that line, nothing more.  `roofline` describes the dominant native kernel
+of the timed region (HIP events on the launch stream, algorithmic bytes of SURVEY.md §8d); it and
+`nmf_iter_gflops` come from the warm-up and timed steps themselves, so every run carries them.
+`--full` then measures what the headline does not need, after the timed region and in this order:
+the device-to-device copy rate of this GPU (`roofline.device_copy_GBps_this_box`, null without it),
+BASELINE configs[1], [2], [4] (`other_configs`, N=1 and fp32 only) and `cpu_baseline`, the CPU
+oracle (oracle/cpu_ref.py, a port of the reference's CPU path) timed on this host on a bounded
+sample (rank 0, N=1 only): minutes, almost all of it the CPU oracle.
 
 `--dump-outputs DIR` writes what the last timed step computed (rank 0) as float32 .npy files, so that two builds
 run with the same arguments can be compared output for output: see `dump_outputs`.
@@ -447,11 +452,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch-per-gpu", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the device copy rate for the roofline, BASELINE configs[1], [2], [4] "
+                         "(`other_configs`) and the CPU oracle (`cpu_baseline`); a plain run does none of these")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU oracle timing (`cpu_baseline`)")
     ap.add_argument("--cpu-all-threads", action="store_true",
-                    help="cpu_baseline: also time the training step with torch.set_num_threads(os.cpu_count()) (minutes on a 256-thread host)")
+                    help="with --full: cpu_baseline also times the training step with torch.set_num_threads(os.cpu_count()) "
+                         "(minutes on a 256-thread host)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the BASELINE configs[1], [2], [4] timings appended to the JSON line as `other_configs`")
+                    help="with --full: skip the BASELINE configs[1], [2], [4] timings appended to the JSON line as `other_configs`")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="f32 (the reference's precision: the headline line) or bf16 = torch.autocast(bfloat16): bf16 "
                          "activation storage, fp32 parameters / statistics / accumulation / NMF internals (BASELINE configs[4] mode)")
@@ -470,6 +480,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.cpu_all_threads and (not args.full or args.no_cpu_baseline):
+        ap.error("--cpu-all-threads times the CPU oracle of --full: it needs --full and no --no-cpu-baseline")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -577,7 +589,7 @@ def main():
     del logits
 
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # context for the roofline fraction: what a plain device-to-device copy of one stage-0 activation
         # (537 MB read + 537 MB written) reaches on THIS box (4.6-5.3 TB/s; the 8 TB/s spec is not reachable)
         src = torch.empty(2 * 32 * 128 ** 3, device=dev)
@@ -672,10 +684,10 @@ def main():
                      if use_dist and os.environ.get("FZ_BENCH_BACKEND", "nccl") == "nccl" else
                      ("gloo" if use_dist else "not initialised (single rank; --force-dist runs it)")),
         }
-        if world == 1 and not args.no_other_configs and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_other_configs and args.dtype == "f32":
             del model, opt, sync, x, target
             out["other_configs"] = other_configs(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_sample(batch=B, all_threads=args.cpu_all_threads)
         if json_fd is not None:
             os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -1,5 +1,6 @@
 """profiles/<name>.md: per-kernel table of one training step from a bench.py JSON line.
-usage: python tools/kernel_table.py <bench.json or log> > profiles/r01_kernel_table.md"""
+usage: python tools/kernel_table.py <bench.json or log> > profiles/r01_kernel_table.md
+(the device-copy rate it quotes is measured by `bench.py --full` only: null in the line of a plain run)"""
 import json
 import sys
 

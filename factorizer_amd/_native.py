@@ -247,6 +247,9 @@ _SIGS.update({
     "fz_sw_gather": ([_vp, _vp] + [_i] * 10 + [_vp], _i),
     "fz_sw_accumulate": ([_vp] * 6 + [_f] + [_i] * 10 + [_vp], _i),
     "fz_sw_finalize": ([_vp, _vp, _i, _i64, _vp], _i),
+    "fz_sw_gather2": ([_vp, _vp] + [_i] * 11 + [_vp], _i),
+    "fz_sw_accumulate2": ([_vp] * 6 + [_f] + [_i] * 11 + [_vp], _i),
+    "fz_sw_finalize2": ([_vp, _vp, _vp, _i, _i64, _i, _vp], _i),
     "fz_mlp_supported": ([_i, _i, _i64], _i),
     "fz_mlp_partials": ([_i, _i64], _i64),
     "fz_mlp_wgrad_rows": ([_i, _i64], _i),

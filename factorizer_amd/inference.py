@@ -7,7 +7,9 @@ the training crop.  MONAI is a third-party dependency that is not under the refe
 published algorithm of `monai.inferers.utils.sliding_window_inference` /
 `compute_importance_map` is restated here with the same constructor arguments.  On device the
 three data movements (window gather, weighted accumulate, final divide) are kernels of
-libfactorizer_hip (csrc/sw_infer.hip); CPU tensors use the composed path.
+libfactorizer_hip (csrc/sw_infer.hip) for images with 1, 2 or 3 spatial axes — the FIVES bundle
+runs the same inferer with roi 512^2 on 2-D images (model_zoo/deconver_fives/configs/
+inference.yaml:77-83) — and fp32 or bf16 data; CPU tensors use the composed path.
 """
 from __future__ import annotations
 
@@ -19,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as N
+from . import composed
 
 
 def _tuple3(v, n):
@@ -70,8 +73,8 @@ def gaussian_factors(roi_size, sigma_scale=0.125, dtype=torch.float32, device="c
 
 
 class SlidingWindowInferer:
-    """`inferer(inputs, network)` with MONAI's argument names.  `inputs` (B, C, D, H, W); the network
-    maps (n, C, *roi) -> (n, C_out, *roi).  mode "gaussian" or "constant"."""
+    """`inferer(inputs, network)` with MONAI's argument names.  `inputs` (B, C, *S) with 1 to 3 spatial axes; the
+    network maps (n, C, *roi) -> (n, C_out, *roi).  mode "gaussian" or "constant"."""
 
     def __init__(self, roi_size, sw_batch_size: int = 1, overlap=0.25, mode: str = "constant",
                  sigma_scale=0.125, padding_mode: str = "constant", cval: float = 0.0, **_ignored):
@@ -88,16 +91,34 @@ class SlidingWindowInferer:
 SlidingWindowInfererAdapt = SlidingWindowInferer  # the bundle's name; no OOM fallback is needed here
 
 
+_NATIVE = (torch.float32, torch.bfloat16)   # storage types of the fz_sw_*2 kernels (FZ_STORE_F32 / FZ_STORE_BF16)
+
+
+def _lift3(t, fill):
+    """(D, H, W)-shaped geometry of the kernels: leading unit axes (extent 1, origin 0) for 1-D and 2-D images"""
+    return (fill,) * (3 - len(t)) + tuple(t)
+
+
+def _weight_map(fac, floor):
+    """dense importance map: ((f0 * f1) * f2 ...) over the axes, clamped from below at the floor"""
+    nd = len(fac)
+    w = fac[0].reshape(-1, *([1] * (nd - 1)))
+    for k in range(1, nd):
+        w = w * fac[k].reshape(*([1] * k), -1, *([1] * (nd - 1 - k)))
+    return w.clamp_min(floor)
+
+
 def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.25, mode="constant",
                              sigma_scale=0.125, padding_mode="constant", cval=0.0, _composed=False):
     nd = inputs.dim() - 2
-    if nd != 3:
-        raise ValueError("sliding_window_inference: 3-D volumes (B, C, D, H, W)")
+    if nd not in (1, 2, 3):
+        raise ValueError("sliding_window_inference: inputs (B, C, *S) with 1, 2 or 3 spatial axes")
     B = inputs.shape[0]
     orig = tuple(inputs.shape[2:])
     roi = tuple(int(r) if r and r > 0 else int(o) for r, o in zip(_tuple3(roi_size, nd), orig))
     ov = _tuple3(overlap, nd)
-    # volumes smaller than the roi are padded symmetrically (remainder at the end), then cropped back
+    # images smaller than the roi are padded symmetrically (remainder at the end), then cropped back; F.pad lists the
+    # last axis first
     pad = []
     for k in range(nd - 1, -1, -1):
         diff = max(roi[k] - orig[k], 0)
@@ -108,24 +129,36 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
             else F.pad(inputs, pad, mode=padding_mode)
     size = tuple(inputs.shape[2:])
     starts = window_starts(size, roi, scan_interval(size, roi, ov))
-    if mode == "gaussian":
-        fac, floor = gaussian_factors(roi, sigma_scale, inputs.dtype, inputs.device)
-    else:
-        fac, floor = [torch.ones(r, dtype=inputs.dtype, device=inputs.device) for r in roi], 1.0
+
+    def factors(dtype, device):
+        if mode == "gaussian":
+            return gaussian_factors(roi, sigma_scale, dtype, device)
+        return [torch.ones(r, dtype=dtype, device=device) for r in roi], 1.0
+
+    fac, floor = factors(inputs.dtype, inputs.device)
     # `_composed` (tests only): stitch a device tensor with framework ops instead of the kernels
-    native = inputs.is_cuda and inputs.dtype == torch.float32 and roi[2] % 4 == 0 and not _composed
+    device = inputs.is_cuda and not _composed
+    native_in = device and inputs.dtype in _NATIVE
+    if device and not native_in:
+        composed.warn_once(f"sw_gather:{inputs.dtype}",
+                           f"sliding_window_inference: {inputs.dtype} inputs are outside the native kernel set (fp32, "
+                           "bf16); gathering the windows with framework ops on device")
     inputs = inputs.contiguous()
-    out = cnt = None
+    size3, roi3 = _lift3(size, 1), _lift3(roi, 1)
+    lib = N.lib() if device else None
+    out = cnt = w = gptr = None
+    native_out = False
     jobs = [(b, s) for b in range(B) for s in starts]
     for j0 in range(0, len(jobs), sw_batch_size):
         chunk = jobs[j0:j0 + sw_batch_size]
-        if native:
+        if native_in:
             win = torch.empty((len(chunk), inputs.shape[1], *roi), dtype=inputs.dtype, device=inputs.device)
+            st, dt = N.stream_ptr(inputs), N.act_dtype(inputs)
             for i, (b, s) in enumerate(chunk):
-                N.check(N.lib().fz_sw_gather(inputs[b].data_ptr(), win[i].data_ptr(), inputs.shape[1], *size, *roi, *s,
-                                             N.stream_ptr(inputs)), "fz_sw_gather")
+                N.check(lib.fz_sw_gather2(inputs[b].data_ptr(), win[i].data_ptr(), inputs.shape[1], *size3, *roi3,
+                                          *_lift3(s, 0), dt, st), "fz_sw_gather2")
         else:
-            win = torch.stack([inputs[b, :, s[0]:s[0] + roi[0], s[1]:s[1] + roi[1], s[2]:s[2] + roi[2]]
+            win = torch.stack([inputs[(b, slice(None)) + tuple(slice(o, o + r) for o, r in zip(s, roi))]
                                for b, s in chunk])
         prob = predictor(win)
         if isinstance(prob, (tuple, list)):
@@ -134,24 +167,39 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
             raise ValueError("sliding_window_inference: the network must keep the window size")
         prob = prob.contiguous()
         if out is None:
-            out = torch.zeros((B, prob.shape[1], *size), dtype=prob.dtype, device=prob.device)
-            cnt = torch.zeros((B, *size), dtype=prob.dtype, device=prob.device)
-        for i, (b, s) in enumerate(chunk):
-            if native and prob.is_cuda and prob.dtype == torch.float32:
-                N.check(N.lib().fz_sw_accumulate(prob[i].data_ptr(), out[b].data_ptr(), cnt[b].data_ptr(),
-                                                 fac[0].data_ptr(), fac[1].data_ptr(), fac[2].data_ptr(), float(floor),
-                                                 prob.shape[1], *size, *roi, *s, N.stream_ptr(prob)),
-                        "fz_sw_accumulate")
+            # native stitching sums the windows in fp32 whatever the network's output type and rounds once at the end
+            native_out = device and prob.is_cuda and prob.dtype in _NATIVE
+            if device and not native_out:
+                composed.warn_once(f"sw_stitch:{prob.dtype}",
+                                   f"sliding_window_inference: {prob.dtype} network outputs are outside the native "
+                                   "kernel set (fp32, bf16); stitching the windows with framework ops on device")
+            acc = torch.float32 if native_out else prob.dtype
+            out = torch.zeros((B, prob.shape[1], *size), dtype=acc, device=prob.device)
+            cnt = torch.zeros((B, *size), dtype=acc, device=prob.device)
+            if native_out:   # fp32 factors, 1.0 on the unit axes of a 1-D / 2-D image
+                fac3 = [torch.ones(1, dtype=torch.float32, device=prob.device)] * (3 - nd) + \
+                    factors(torch.float32, prob.device)[0]
+                gptr = [f.data_ptr() for f in fac3]
             else:
-                w = (fac[0][:, None, None] * fac[1][None, :, None] * fac[2][None, None, :]).clamp_min(floor)
-                sl = (slice(s[0], s[0] + roi[0]), slice(s[1], s[1] + roi[1]), slice(s[2], s[2] + roi[2]))
+                w = _weight_map(fac, floor)
+        if native_out:
+            st, dt = N.stream_ptr(prob), N.act_dtype(prob)
+        for i, (b, s) in enumerate(chunk):
+            if native_out:
+                N.check(lib.fz_sw_accumulate2(prob[i].data_ptr(), out[b].data_ptr(), cnt[b].data_ptr(), *gptr,
+                                              float(floor), prob.shape[1], *size3, *roi3, *_lift3(s, 0), dt, st),
+                        "fz_sw_accumulate2")
+            else:
+                sl = tuple(slice(o, o + r) for o, r in zip(s, roi))
                 out[(b, slice(None)) + sl] += w * prob[i]
                 cnt[(b,) + sl] += w
-    V = size[0] * size[1] * size[2]
-    if native and out.is_cuda and out.dtype == torch.float32:
+    if native_out:
+        res = out if prob.dtype == torch.float32 else torch.empty(out.shape, dtype=prob.dtype, device=out.device)
+        V = math.prod(size)
         for b in range(B):
-            N.check(N.lib().fz_sw_finalize(out[b].data_ptr(), cnt[b].data_ptr(), out.shape[1], V, N.stream_ptr(out)),
-                    "fz_sw_finalize")
+            N.check(lib.fz_sw_finalize2(out[b].data_ptr(), cnt[b].data_ptr(), res[b].data_ptr(), out.shape[1], V,
+                                        N.act_dtype(res), N.stream_ptr(out)), "fz_sw_finalize2")
+        out = res
     else:
         out = out / cnt[:, None]
     if any(pad):

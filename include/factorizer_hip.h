@@ -609,6 +609,20 @@ int fz_sw_accumulate(const float* prob, float* out, float* cnt, const float* gz,
                      float wmin, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0,
                      fz_stream_t stream);
 int fz_sw_finalize(float* out, const float* cnt, int C, int64_t V, fz_stream_t stream);
+/* The same three steps for 1-D, 2-D and 3-D images, any window width and origin, fp32 or bf16 windows (FIVES:
+ * SlidingWindowInfererAdapt(roi 512^2, overlap 0.5, mode "gaussian"), model_zoo/deconver_fives/configs/inference.yaml:77-83).
+ * A 2-D image is passed as (C, 1, H, W) with gz = {1.0f}, a 1-D one as (C, 1, 1, L) with gz = gy = {1.0f}: the weight
+ * (1 * gy) * gx is gy * gx bit for bit.  act_dtype (FZ_STORE_F32 / FZ_STORE_BF16) is the storage type of `img` / `win`
+ * (gather: a byte-exact copy), of `prob` (accumulate) and of `res` (finalize); `out` and `cnt` are always fp32, so the
+ * overlapping windows are summed in fp32 and the result is rounded once.  finalize writes out / cnt into `res`: fp32 may
+ * be `out` itself (in place), bf16 needs a tensor of its own.  With 3-D fp32 data the results equal those of the three
+ * calls above bit for bit.  FZ_E_SHAPE for a window outside the image, FZ_E_ARG for a null pointer or another act_dtype. */
+int fz_sw_gather2(const void* img, void* win, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0,
+                  int act_dtype, fz_stream_t stream);
+int fz_sw_accumulate2(const void* prob, float* out, float* cnt, const float* gz, const float* gy, const float* gx,
+                      float wmin, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0, int act_dtype,
+                      fz_stream_t stream);
+int fz_sw_finalize2(const float* out, const float* cnt, void* res, int C, int64_t V, int act_dtype, fz_stream_t stream);
 
 /* ---- AdamW over one flat buffer (torch.optim.AdamW of the training recipe,
  * model_zoo/factorizer_brats23/configs/train.yaml:72-76).  step >= 1 is the 1-based update count;

@@ -24,24 +24,21 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
 #    lanes 48-63 on gfx950; replacing exactly those four instructions by scalar adds in the assembly restores bitwise replay,
 #    s_nop padding around them does not (tools/probes/upcat_asm_variants.py, profiles/r04_nondeterminism.md).
 #    tools/pk_opsel_audit.py counts such instructions in the built objects; tests/test_no_spills.py keeps the count at zero.
-#  * gemm.hip: it pairs accumulator elements of DIFFERENT MFMA tiles for v_pk_* math, which needs register-to-register copies of
-#    whole accumulator tiles — +64..128 VGPRs and scratch spills in the fused epilogues (round 1);
+#  * the fp32-MFMA GEMM units (gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain.hip, gemm_dw.hip): it pairs accumulator elements
+#    of DIFFERENT MFMA tiles for v_pk_* math, which needs register-to-register copies of whole accumulator tiles — +64..128 VGPRs
+#    and scratch spills in the fused epilogues (round 1);
 #  * the NMF wave programs: v_pk_fma_f32 / v_pk_mul_f32 pairs whose 64-bit register alignment costs more v_mov than the packing
 #    saves: the rank-2 HALS backward of the generic-patch core went from 234 to 154 VGPRs and 43.9 -> 38.3 ms per cfg-5 step (round 3).
 # Exception (SLP left on): gemm_bx.hip — without it the compile does not finish in five minutes, and the audit finds no such
 # instruction in it.  (The standalone ft.NMF units nmf_r*.hip were an exception at first — round 3 believed they spill more
 # without SLP; measured in round 4 they spill LESS: 34 kernels / 12.6 KB of scratch against 51 / 49 KB — and carried 17 000 of
 # the op_sel'd instructions.)
-_NO_SLP = ["-fno-slp-vectorize"]
 _SLP_ON = {"gemm_bx.hip"}
 
 
-class _PerFile(dict):
-    def get(self, src, default=None):
-        return [] if src in _SLP_ON else _NO_SLP
-
-
-PER_FILE_FLAGS = _PerFile()
+def flags_of(src: str) -> list:
+    """hipcc flags of one translation unit (by file name)"""
+    return FLAGS if src in _SLP_ON else [*FLAGS, "-fno-slp-vectorize"]
 
 
 def _hipcc() -> str:
@@ -55,47 +52,34 @@ def sources():
     return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
-def _deps_mtime() -> float:
+def _newest(suffixes) -> float:
     m = 0.0
     for root in (CSRC, os.path.join(os.path.dirname(HERE), "include")):
         for f in os.listdir(root):
-            if f.endswith((".h", ".inc", ".hip")):
+            if f.endswith(suffixes):
                 m = max(m, os.path.getmtime(os.path.join(root, f)))
     return m
-
-
-def _flags_of(src):
-    return " ".join([*FLAGS, *PER_FILE_FLAGS.get(src, [])])
 
 
 def _stale_flags() -> bool:
     """an object compiled with other flags than today's (the .flags stamp beside it) makes the library stale"""
     for src in sources():
         stamp = os.path.join(OBJ, src[:-4] + ".o.flags")
-        if not os.path.exists(stamp) or open(stamp).read() != _flags_of(src):
+        if not os.path.exists(stamp) or open(stamp).read() != " ".join(flags_of(src)):
             return True
     return False
 
 
 def needs_build() -> bool:
-    return not os.path.exists(LIB) or os.path.getmtime(LIB) < _deps_mtime() or _stale_flags()
-
-
-def _hdr_mtime() -> float:
-    m = 0.0
-    for root in (CSRC, os.path.join(os.path.dirname(HERE), "include")):
-        for f in os.listdir(root):
-            if f.endswith((".h", ".inc")):
-                m = max(m, os.path.getmtime(os.path.join(root, f)))
-    return m
+    return not os.path.exists(LIB) or os.path.getmtime(LIB) < _newest((".h", ".inc", ".hip")) or _stale_flags()
 
 
 def _compile(src: str) -> str:
     obj = os.path.join(OBJ, src[:-4] + ".o")
-    flags = [*FLAGS, *PER_FILE_FLAGS.get(src, [])]
+    flags = flags_of(src)
     stamp, want = obj + ".flags", " ".join(flags)   # an object built with other flags is stale, whatever its age
     fresh = os.path.exists(stamp) and open(stamp).read() == want
-    if fresh and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(os.path.join(CSRC, src)), _hdr_mtime()):
+    if fresh and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(os.path.join(CSRC, src)), _newest((".h", ".inc"))):
         return obj
     cmd = [_hipcc(), *flags, "-c", os.path.join(CSRC, src), "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -111,7 +95,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int | None = None) ->
         return LIB
     os.makedirs(OBJ, exist_ok=True)
     srcs = sources()
-    jobs = jobs or min(len(srcs), os.cpu_count() or 4)
+    jobs = jobs or min(len(srcs), int(os.environ.get("MAX_JOBS") or 0) or min(os.cpu_count() or 4, 16))
     if verbose:
         print(f"[factorizer_amd] hipcc {ARCH}: {len(srcs)} translation units, {jobs} jobs", flush=True)
     with cf.ThreadPoolExecutor(jobs) as ex:

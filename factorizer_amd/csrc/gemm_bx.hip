@@ -2,7 +2,7 @@
 //
 //   Out[m, n] = epilogue( Σ_k A[m, k] · prologue(In)[k, n] )        n = voxel (column)
 //
-// Same layers as gemm.hip's streaming kernel (reference call sites: layers/linear.py:53-58, factorizer.py:38,53,116,
+// Same layers as the streaming kernel of gemm_stream.hip (reference call sites: layers/linear.py:53-58, factorizer.py:38,53,116,
 // layers/mlp.py:54-63, unet.py:53,123,128 and autograd through them) for reduction lengths K >= 64, i.e. every dense
 // layer and k2s2 (transposed) convolution of stages 1-4 of the U-shape.
 //
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bx_kernel(GemmArgsT<AT> p) {
   const int j = lane & 31, h = lane >> 5;
   const int tiles_per_sample = (int)((p.Ncol + TN * 4 - 1) / (TN * 4));
   int bx = blockIdx.x, by = blockIdx.y;
-  if (p.ygroups > 1) {   // XCD-aware: the row-block groups of one column tile share an XCD's L2 (gemm.hip)
+  if (p.ygroups > 1) {   // XCD-aware: the row-block groups of one column tile share an XCD's L2 (gemm_stream.hip)
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     by = slot % p.ygroups;
     bx = (slot / p.ygroups) * 8 + xcd;

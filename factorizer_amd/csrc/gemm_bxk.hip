@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bxk_kernel(GemmArgsT<AT> p) {
   const int j = lane & 31, h = lane >> 5;
   const int tiles_per_sample = (int)((p.Ncol + TN - 1) / TN);
   int bx = blockIdx.x, by = blockIdx.y;
-  if (p.ygroups > 1) {   // XCD-aware: the row-block groups of one column tile share an XCD's L2 (gemm.hip)
+  if (p.ygroups > 1) {   // XCD-aware: the row-block groups of one column tile share an XCD's L2 (gemm_stream.hip)
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     by = slot % p.ygroups;
     bx = (slot / p.ygroups) * 8 + xcd;

@@ -1,5 +1,5 @@
 // gemm_common.h — argument block, operand fetch and epilogue helpers shared by the channels-first GEMM
-// kernels (gemm.hip: fp32 MFMA family; gemm_bx.hip: split-bf16 MFMA family).
+// kernels (gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain.hip, gemm_dw.hip: fp32 MFMA family; gemm_bx.hip: split-bf16 MFMA family).
 #pragma once
 #include <cstdlib>
 
@@ -303,5 +303,9 @@ __device__ __forceinline__ void store_block(const GemmArgsT<AT>& p, const f32x16
 // split-bf16 MFMA family (gemm_bx.hip); pro: 0 none, 1 LayerNorm, 2 GELU, 3 ReLU gate (bmul)
 template <typename AT>
 int gemm_bx_launch(const GemmArgsT<AT>& a, int loader, int epilogue, int pro, fz_stream_t stream);
+
+// streaming kernel of the fp32 MFMA family (gemm_stream.hip): the last stop of fz_gemm's dispatcher (gemm.hip)
+template <typename AT>
+int gemm_stream_launch(const fz_gemm_desc* d, GemmArgsT<AT> a, fz_stream_t stream);
 
 }  // namespace fz

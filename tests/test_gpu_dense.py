@@ -1,4 +1,4 @@
-"""-m gpu: the fp32-MFMA GEMM family (csrc/gemm.hip, wgrad.hip, ln.hip) behind the layer
+"""-m gpu: the fp32-MFMA GEMM family (csrc/gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain.hip, gemm_dw.hip, wgrad.hip, ln.hip) behind the layer
 Functions of factorizer_amd/pointwise.py, against ATen on CPU (the arithmetic the reference
 runs: nn.Conv1d / nn.LayerNorm / nn.Conv3d / nn.ConvTranspose3d) and the reference goldens."""
 import pytest
@@ -314,7 +314,7 @@ def test_dice_ce_loss_fused(C):
 @pytest.mark.parametrize("C,Hd", [(32, 64), (32, 128), (64, 128)])
 @pytest.mark.parametrize("B,S", [(2, (8, 8, 8)), (1, (6, 4, 5)), (2, (16, 16, 12))])
 def test_mlp_chain_kernel(B, S, C, Hd):
-    """fz_mlp_chain (csrc/gemm.hip gemm_chain_kernel) against the layer-by-layer CPU composition
+    """fz_mlp_chain (csrc/mlp_chain.hip gemm_chain_kernel) against the layer-by-layer CPU composition
     x + fc2(gelu(fc1(LN(x)))) (factorizer.py:76, mlp.py:54-60, norm.py:29-34): forward, the saved
     pre-activation / statistics, and the backward chain (gz1, gx1, dγ, dβ).  V = 120 and 3072 cover
     partial column tiles."""

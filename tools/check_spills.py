@@ -18,7 +18,7 @@ def main():
     bad = 0
     for f in files:
         with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
-            cmd = [B._hipcc(), *B.FLAGS, *B.PER_FILE_FLAGS.get(os.path.basename(f), []), "-I", os.path.join(ROOT, "include"),
+            cmd = [B._hipcc(), *B.flags_of(os.path.basename(f)), "-I", os.path.join(ROOT, "include"),
                    "--cuda-device-only", "-S", f, "-o", tmp.name]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode:

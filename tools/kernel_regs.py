@@ -13,7 +13,7 @@ from factorizer_amd import build as B  # noqa: E402
 f = sys.argv[1]
 sub = sys.argv[2] if len(sys.argv) > 2 else ""
 with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
-    cmd = [B._hipcc(), *B.FLAGS, *B.PER_FILE_FLAGS.get(os.path.basename(f), []), "--cuda-device-only", "-S", f, "-o", tmp.name]
+    cmd = [B._hipcc(), *B.flags_of(os.path.basename(f)), "--cuda-device-only", "-S", f, "-o", tmp.name]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-3000:])

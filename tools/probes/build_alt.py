@@ -21,7 +21,7 @@ def one(src):
     if src not in files:
         return os.path.join(B.OBJ, src[:-4] + ".o")
     obj = os.path.join(alt, src[:-4] + ".o")
-    cmd = [B._hipcc(), *B.FLAGS, *B.PER_FILE_FLAGS.get(src, []), *flag, "-c", os.path.join(B.CSRC, src), "-o", obj]
+    cmd = [B._hipcc(), *B.flags_of(src), *flag, "-c", os.path.join(B.CSRC, src), "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-3000:])

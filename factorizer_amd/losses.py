@@ -85,6 +85,9 @@ def dice_bce_loss(logits, target, smooth: float = 1e-5):
     if logits.is_cuda and logits.numel() and logits.dtype == torch.float32 and target.dtype == torch.float32 \
             and (logits.numel() // planes) % 4 == 0:
         return DiceBCEFn.apply(logits, target, smooth)
+    if logits.is_cuda and logits.numel():
+        from .composed import warn_once
+        warn_once("dice_bce_loss", f"no native kernel for shape {tuple(logits.shape)} / {logits.dtype}: composed framework ops")
     return dice_bce_loss_composed(logits, target, smooth)
 
 

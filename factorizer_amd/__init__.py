@@ -14,6 +14,8 @@ from .layers import MLP, LayerNorm, Linear, PosEmbed, PositionalEmbedding
 from .convs import Conv2d, Conv3d, ConvTranspose2d, ConvTranspose3d
 from .blocks import FactMixer, FactorizerBlock, FactorizerStage
 from .losses import DiceCELoss, dice_bce_loss, dice_ce_loss
+from .metrics import (DiceMetric, HausdorffDistanceMetric, dice_metric, discretize, hausdorff_distance, mask_edges,
+                      segmentation_counts)
 from .training import FlatAdamW, WarmupCosineSchedule, load_checkpoint, load_checkpoints
 from .parallel import FlatGradSync
 from .inference import SlidingWindowInferer, SlidingWindowInfererAdapt, sliding_window_inference

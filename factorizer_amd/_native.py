@@ -293,5 +293,13 @@ _SIGS.update({
     "fz_dropout_bits_words": ([_i, _i, _i64], _i64),
     "fz_dropout_keep_bits": ([_vp, _i, _i, _i, _i64, _f, _vp, _vp], _i),
     "fz_dropout_apply": ([_i, _vp, _f, _vp, _vp, _vp, _i, _i, _i64, _i, _vp], _i),
+    "fz_seg_counts_chunks": ([_i64], _i),
+    "fz_seg_counts_workspace_bytes": ([_i, _i64], _i64),
+    "fz_seg_counts": ([_vp, _i, _vp, _i, _f, _vp, _vp, _vp, _i, _i64, _vp], _i),
+    "fz_mask_edges": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "fz_edge_min_dist2_splits": ([_i64, _i64], _i),
+    "fz_edge_min_dist2_workspace_bytes": ([_i64, _i64], _i64),
+    "fz_edge_min_dist2": ([_vp, _i64, _vp, _i64, _f, _f, _f, _vp, _vp, _vp], _i),
 })
+SEG_F32, SEG_BF16, SEG_U8 = 0, 1, 2   # include/factorizer_hip.h: FZ_SEG_* element kinds of fz_seg_counts
 DROP_RES, DROP_GELU, DROP_GELU_BWD = 0, 1, 2   # include/factorizer_hip.h: FZ_DROP_*

@@ -634,3 +634,65 @@ def dropout_apply(kind, bits, p, t, aux=None):
             N.stream_ptr(t)), cols=B * V)
     N.check(rc, "fz_dropout_apply")
     return y
+
+
+# ---- segmentation metrics (csrc/segmetric.hip) ------------------------------------------------------------------------
+_SEG_KIND = {torch.float32: N.SEG_F32, torch.bfloat16: N.SEG_BF16, torch.uint8: N.SEG_U8, torch.bool: N.SEG_U8}
+
+
+def seg_kind_ok(t) -> bool:
+    """the element kinds fz_seg_counts reads: fp32 / bf16 values, uint8 / bool masks"""
+    return t.dtype in _SEG_KIND
+
+
+def seg_counts(pred, label, bound, want_mask=False, want_counts=True):
+    """One pass of fz_seg_counts over `pred` (B, C, *S) — logits of a native float kind (foreground iff x >= bound) or a
+    one-byte mask (foreground iff non-zero) — and the optional `label` (non-zero counts).  Returns (counts, mask): int64
+    (B, C, 3) = {|P ∧ Y|, |P|, |Y|} or None, uint8 mask shaped like `pred` or None."""
+    B, C = pred.shape[:2]
+    planes = B * C
+    V = pred.numel() // planes
+    lib = N.lib()
+    ws = torch.empty(int(lib.fz_seg_counts_workspace_bytes(planes, V)) // 4, dtype=torch.int32, device=pred.device)
+    counts = torch.empty((B, C, 3), dtype=torch.int64, device=pred.device) if want_counts else None
+    mask = torch.empty(pred.shape, dtype=torch.uint8, device=pred.device) if want_mask else None
+    nbytes = pred.numel() * pred.element_size() + (label.numel() * label.element_size() if label is not None else 0) + \
+        (pred.numel() if want_mask else 0)
+    with _dev_guard(pred):
+        rc = _timed("seg_counts", nbytes, lambda: lib.fz_seg_counts(
+            pred.data_ptr(), _SEG_KIND[pred.dtype], N.ptr(label), _SEG_KIND[label.dtype] if label is not None else 0,
+            float(bound), N.ptr(mask), ws.data_ptr(), N.ptr(counts), planes, V, N.stream_ptr(pred)), cols=B * V)
+    N.check(rc, "fz_seg_counts")
+    return counts, mask
+
+
+def mask_edges(mask):
+    """fz_mask_edges over a one-byte mask (B, C, *S) with 1 to 3 spatial axes: (edges uint8 like mask, counts int64 (B, C))"""
+    B, C = mask.shape[:2]
+    sp = tuple(mask.shape[2:])
+    nd = len(sp)
+    d3 = (1,) * (3 - nd) + sp
+    edges = torch.empty(mask.shape, dtype=torch.uint8, device=mask.device)
+    counts = torch.empty((B, C), dtype=torch.int64, device=mask.device)
+    with _dev_guard(mask):
+        rc = _timed("mask_edges", 2 * mask.numel(), lambda: N.lib().fz_mask_edges(
+            mask.data_ptr(), edges.data_ptr(), counts.data_ptr(), B * C, nd, *d3, N.stream_ptr(mask)),
+            cols=B * math.prod(sp))
+    N.check(rc, "fz_mask_edges")
+    return edges, counts
+
+
+def edge_min_dist2(q, t, w):
+    """fz_edge_min_dist2: q (nq, 4), t (nt, 4) fp32 coordinate lists (nq, nt >= 1), w = the three squared spacings; returns
+    the fp32 (nq,) minimum over t of Σ_k w_k (q_k − t_k)²"""
+    nq, nt = q.shape[0], t.shape[0]
+    lib = N.lib()
+    out = torch.empty(nq, dtype=torch.float32, device=q.device)
+    nws = int(lib.fz_edge_min_dist2_workspace_bytes(nq, nt))
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=q.device) if nws else None
+    with _dev_guard(q):
+        rc = _timed("edge_min_dist2", 16 * (nq + nt) + 4 * nq, lambda: lib.fz_edge_min_dist2(
+            q.data_ptr(), nq, t.data_ptr(), nt, float(w[0]), float(w[1]), float(w[2]), out.data_ptr(), N.ptr(ws),
+            N.stream_ptr(q)), cols=nq)
+    N.check(rc, "fz_edge_min_dist2")
+    return out

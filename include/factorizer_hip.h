@@ -624,6 +624,44 @@ int fz_sw_accumulate2(const void* prob, float* out, float* cnt, const float* gz,
                       fz_stream_t stream);
 int fz_sw_finalize2(const float* out, const float* cnt, void* res, int C, int64_t V, int act_dtype, fz_stream_t stream);
 
+/* ---- segmentation metrics of the recipe (csrc/segmetric.hip) -------------------------------------------------------
+ * Every training iteration: Activationsd(sigmoid) -> AsDiscreted(threshold=0.5) -> MeanDice(include_background=True)
+ * (model_zoo/factorizer_brats23/configs/train.yaml:215-243); every validation pass: the same Dice and
+ * MeanHausdorffDistance(percentile=95) on the stitched prediction (train.yaml:245-287).
+ *
+ * fz_seg_counts: pred, label (planes, V) dense.  Element kinds FZ_SEG_F32 / FZ_SEG_BF16 / FZ_SEG_U8 (one byte: uint8 or
+ *   bool).  A float pred element is foreground iff (float)x >= bound — the caller moves the threshold through the inverse
+ *   sigmoid, bound = log(t / (1 - t)), so no transcendental runs on device; a FZ_SEG_U8 pred is a discrete mask, foreground
+ *   iff non-zero (bound unused).  A label element counts iff it is non-zero, whatever its kind.  label may be NULL (its
+ *   counts are then 0).  mask (planes, V) uint8, optional: the 0 / 1 decision, written by the same pass.  counts
+ *   (planes, 3) int64, optional: {|P and Y|, |P|, |Y|}, exact integers, bitwise reproducible (no float atomics: uint32
+ *   partials per workgroup in `workspace`, fz_seg_counts_workspace_bytes(planes, V) bytes, always required, added in a
+ *   fixed order by a second launch).  16-byte loads when every plane starts 16-byte aligned and holds a multiple of 8
+ *   elements (or planes == 1: the last V % 8 elements take a masked tail); any other V or alignment runs one element per
+ *   lane.  FZ_E_ARG: null pred / workspace, neither output requested, bad kind, NaN bound; FZ_E_SHAPE: sizes.
+ * fz_mask_edges: mask, edges (planes, D, H, W) uint8 (distinct buffers); nd = 1, 2 or 3 spatial axes, a 2-D image passed
+ *   as (1, H, W), a 1-D one as (1, 1, L).  edges = 1 where the mask is non-zero and one of the 2 nd face neighbours is
+ *   zero or outside the image (mask ^ binary_erosion(mask), cross element, zero border), else 0; counts (planes) int64 =
+ *   edge voxels per plane (zeroed by the call).
+ * fz_edge_min_dist2: q (nq, 4), t (nt, 4) fp32, 16-byte aligned: integer voxel coordinates in columns 0..2, 0 in unused
+ *   columns.  out (nq) = min over t of w0 dx^2 + w1 dy^2 + w2 dz^2 with w = spacing^2, in fp32; independent of the order
+ *   of either list.  With w = (1, 1, 1) and coordinates below 2048 every intermediate is an integer < 2^24: exact.
+ *   Long target lists are split over fz_edge_min_dist2_splits(nq, nt) workgroup rows whose partial minima (workspace:
+ *   fz_edge_min_dist2_workspace_bytes(nq, nt) bytes, 0 when there is one split) are combined in split order. */
+#define FZ_SEG_F32 0
+#define FZ_SEG_BF16 1
+#define FZ_SEG_U8 2
+int fz_seg_counts_chunks(int64_t V);
+int64_t fz_seg_counts_workspace_bytes(int planes, int64_t V);
+int fz_seg_counts(const void* pred, int pred_kind, const void* label, int label_kind, float bound, uint8_t* mask,
+                  void* workspace, int64_t* counts, int planes, int64_t V, fz_stream_t stream);
+int fz_mask_edges(const uint8_t* mask, uint8_t* edges, int64_t* counts, int planes, int nd, int D, int H, int W,
+                  fz_stream_t stream);
+int fz_edge_min_dist2_splits(int64_t nq, int64_t nt);
+int64_t fz_edge_min_dist2_workspace_bytes(int64_t nq, int64_t nt);
+int fz_edge_min_dist2(const float* q, int64_t nq, const float* t, int64_t nt, float w0, float w1, float w2, float* out,
+                      void* workspace, fz_stream_t stream);
+
 /* ---- AdamW over one flat buffer (torch.optim.AdamW of the training recipe,
  * model_zoo/factorizer_brats23/configs/train.yaml:72-76).  step >= 1 is the 1-based update count;
  * grad_scale multiplies the gradient first (1/world after a summed all-reduce). */

@@ -16,6 +16,8 @@ from .blocks import FactMixer, FactorizerBlock, FactorizerStage
 from .losses import DiceCELoss, dice_bce_loss, dice_ce_loss
 from .metrics import (DiceMetric, HausdorffDistanceMetric, dice_metric, discretize, hausdorff_distance, mask_edges,
                       segmentation_counts)
+from .augment import (AugmentParams, BatchAugment, affine_resample, augment_batch, draw_augment_params, gaussian_noise_field,
+                      gaussian_smooth)
 from .training import FlatAdamW, WarmupCosineSchedule, load_checkpoint, load_checkpoints
 from .parallel import FlatGradSync
 from .inference import SlidingWindowInferer, SlidingWindowInfererAdapt, sliding_window_inference

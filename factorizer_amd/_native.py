@@ -300,6 +300,10 @@ _SIGS.update({
     "fz_edge_min_dist2_splits": ([_i64, _i64], _i),
     "fz_edge_min_dist2_workspace_bytes": ([_i64, _i64], _i64),
     "fz_edge_min_dist2": ([_vp, _i64, _vp, _i64, _f, _f, _f, _vp, _vp, _vp], _i),
+    "fz_aug_record_floats": ([], _i),
+    "fz_aug_resample": ([_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp], _i),
+    "fz_aug_smooth": ([_vp, _vp, _i, _i, _vp, _vp] + [_i] * 6 + [_vp], _i),
+    "fz_aug_noise_field": ([_vp, _vp, _i, _i, _i64, _vp], _i),
 })
 SEG_F32, SEG_BF16, SEG_U8 = 0, 1, 2   # include/factorizer_hip.h: FZ_SEG_* element kinds of fz_seg_counts
 DROP_RES, DROP_GELU, DROP_GELU_BWD = 0, 1, 2   # include/factorizer_hip.h: FZ_DROP_*

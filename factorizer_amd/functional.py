@@ -696,3 +696,49 @@ def edge_min_dist2(q, t, w):
             N.stream_ptr(q)), cols=nq)
     N.check(rc, "fz_edge_min_dist2")
     return out
+
+
+# ---- batch augmentations (csrc/augment.hip) ---------------------------------------------------------------------------
+def aug_noise_field(seed, B, C, V):
+    """fz_aug_noise_field: fp32 (B, C, V) normals of the int64 device tensor `seed` (factorizer_amd/augment.py)"""
+    out = torch.empty((B, C, V), dtype=torch.float32, device=seed.device)
+    with _dev_guard(seed):
+        rc = _timed("aug_noise_field", 4 * out.numel(), lambda: N.lib().fz_aug_noise_field(
+            out.data_ptr(), seed.data_ptr(), int(B), int(C), int(V), N.stream_ptr(seed)), cols=B * V)
+    N.check(rc, "fz_aug_noise_field")
+    return out
+
+
+def aug_apply(image, label, records, table_words, ns, seed):
+    """fz_aug_resample over the whole batch, then fz_aug_smooth over its `ns` smoothing samples (ns = 0: no second launch).
+    `records`: the device copy of augment._records — `table_words` fp32 words of per-sample records, the int32 sample list of
+    the smoothing slots behind them.  image (B, C, *S) fp32 / bf16 and label (B, L, *S) uint8 / bool, contiguous, either may
+    be None; seed: int64 device tensor or None (no noise).  Returns new (image, label)."""
+    lib = N.lib()
+    ref = image if image is not None else label
+    B = ref.shape[0]
+    sp = tuple(ref.shape[2:])
+    nd = len(sp)
+    d3 = (1,) * (3 - nd) + sp
+    V = math.prod(sp)
+    C = image.shape[1] if image is not None else 0
+    L = label.shape[1] if label is not None else 0
+    if int(lib.fz_aug_record_floats()) * B != table_words:
+        raise N.NativeError("the record layout of augment.py and of the library differ")
+    out_i = torch.empty_like(image) if image is not None else None
+    out_l = torch.empty_like(label) if label is not None else None
+    ns = ns if image is not None else 0
+    ws = torch.empty((ns, C, V), dtype=torch.float32, device=ref.device) if ns else None
+    dt = N.act_dtype(image) if image is not None else N.STORE_F32
+    es = image.element_size() if image is not None else 0
+    with _dev_guard(ref):
+        rc = _timed("aug_resample", B * V * (2 * C * es + 2 * L), lambda: lib.fz_aug_resample(
+            N.ptr(image), N.ptr(out_i), dt, C, N.ptr(label), N.ptr(out_l), L, records.data_ptr(), N.ptr(seed), N.ptr(ws), ns,
+            B, nd, *d3, N.stream_ptr(ref)), cols=B * V)
+        N.check(rc, "fz_aug_resample")
+        if ns:
+            rc = _timed("aug_smooth", ns * C * V * (4 + es), lambda: lib.fz_aug_smooth(
+                ws.data_ptr(), out_i.data_ptr(), dt, C, records.data_ptr(), records.data_ptr() + 4 * table_words, ns, B, nd,
+                *d3, N.stream_ptr(ref)), cols=ns * V)
+            N.check(rc, "fz_aug_smooth")
+    return out_i, out_l

@@ -662,6 +662,41 @@ int64_t fz_edge_min_dist2_workspace_bytes(int64_t nq, int64_t nt);
 int fz_edge_min_dist2(const float* q, int64_t nq, const float* t, int64_t nt, float w0, float w1, float w2, float* out,
                       void* workspace, fz_stream_t stream);
 
+/* ---- random training augmentations of the recipe, on device (csrc/augment.hip; semantics: factorizer_amd/augment.py) ----
+ * `random_transforms` of every bundle (model_zoo/factorizer_brats23/configs/train.yaml): RandAffined, RandGaussianNoised,
+ * RandGaussianSmoothd, RandScaleIntensityd, RandShiftIntensityd, one RandFlipd per axis — for a whole batch at once.
+ * image (B, C, D, H, W) of act_dtype, label (B, L, D, H, W) uint8 (or bool); nd = 2 or 3 spatial axes, a 2-D image is passed
+ * as D = 1; every extent <= 2048 and fewer than 2^31 voxels per plane (FZ_E_UNSUPPORTED beyond: in-plane offsets are 32-bit).
+ * table: B records of fz_aug_record_floats() = 48 fp32 values in DEVICE memory (one host-to-device copy per batch):
+ *   [0..8]   A, 3 x 3 row-major over (z, y, x); a 2-D matrix sits in rows / columns 1..2 with A[0] = 1
+ *   [9..11]  flip of z, y, x (non-zero: flipped)          [12] noise std (<= 0: none)      [13] gain      [14] offset
+ *   [15]     smoothing slot of the sample (0 .. ns - 1), -1: the sample does not smooth
+ *   [16..18] tail of the z, y, x taps (0: that axis is not smoothed; at most 4)
+ *   [19..45] taps of z, y, x, nine each, centre at index 4, zeros beyond the tail        [46..47] unused
+ * fz_aug_resample: output voxel o reads the source position p = A (o' - c) + c with o' = o mirrored on the flipped axes and
+ *   c_k = (N_k - 1) / 2, clamped per axis to [0, N_k - 1] (border padding).  Image planes: (bi/tri)linear, fp32 weights and
+ *   sums; label planes: the voxel at floor(p + 0.5).  A record whose A is exactly the identity copies (or mirrors) without
+ *   arithmetic: bit for bit.  Then image += std z(b, c, v) where seed != NULL and std > 0 — z: word v & 3 of Philox4x32-10
+ *   (csrc/fz_philox.h) with counter (v >> 2, c, b, 0x41554731) and key (seed lo, seed hi) of the int64 at `seed` (device
+ *   memory), turned into normals by two Box-Muller pairs per counter: u_i = ((w_i >> 8) + 0.5) 2^-24,
+ *   (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), likewise (u2, u3) -> (z2, z3); v is the flat OUTPUT voxel.  A sample
+ *   without a smoothing slot then stores image gain + offset (one FMA; skipped when gain = 1 and offset = 0) to img_out; a
+ *   sample with slot i stores its fp32 values to smooth_ws (ns, C, D, H, W) slot i instead and leaves img_out to
+ *   fz_aug_smooth.  One launch covers all planes of all samples.  C = 0 (no image) or L = 0 (no label) is allowed, not both.
+ * fz_aug_smooth: for i < ns, sample b = list[i] (device int32; entries outside 0 .. B - 1 are skipped): separable
+ *   convolution of smooth_ws slot i with the record's taps along every axis whose tail is > 0, zero padding, fp32, then
+ *   gain / offset, stored to img_out sample b in act_dtype (one rounding).  One launch: a workgroup holds an output tile and
+ *   its 4-voxel halo in LDS for all passes.  ns = 0 launches nothing.
+ * fz_aug_noise_field: out (B, C, V) fp32 = z(b, c, v) alone.
+ * FZ_E_ARG: null pointer, aliasing input / output, bad act_dtype, nd outside {2, 3}; FZ_E_SHAPE: sizes, an extent above 2048. */
+int fz_aug_record_floats(void);
+int fz_aug_resample(const void* img, void* img_out, int act_dtype, int C, const uint8_t* lab, uint8_t* lab_out, int L,
+                    const float* table, const int64_t* seed, float* smooth_ws, int ns, int B, int nd, int D, int H, int W,
+                    fz_stream_t stream);
+int fz_aug_smooth(const float* smooth_ws, void* img_out, int act_dtype, int C, const float* table, const int32_t* list, int ns,
+                  int B, int nd, int D, int H, int W, fz_stream_t stream);
+int fz_aug_noise_field(float* out, const int64_t* seed, int B, int C, int64_t V, fz_stream_t stream);
+
 /* ---- AdamW over one flat buffer (torch.optim.AdamW of the training recipe,
  * model_zoo/factorizer_brats23/configs/train.yaml:72-76).  step >= 1 is the 1-based update count;
  * grad_scale multiplies the gradient first (1/world after a summed all-reduce). */

@@ -75,7 +75,7 @@ class FactorizerBlock(nn.Module):
     def _fusable(self, x) -> bool:
         """Standard Swin block on a device tensor (fp32, or bf16 activations with fp32 parameters): LayerNorm / ReLU / exact GELU, no live
         dropout or live torch.nn.Dropout with p < 1 — then LayerNorm, bias, ReLU, GELU and both residual adds are fused into the GEMM
-        kernels (csrc/gemm.hip, csrc/mlp_chain.hip) instead of running as separate full-tensor passes; live dropout only on the one-node path."""
+        kernels (csrc/gemm.hip, csrc/mlp_chain32.hip) instead of running as separate full-tensor passes; live dropout only on the one-node path."""
         f, m = self.fact, self.mlp
         if not (x.is_cuda and x.numel() and x.dtype in (torch.float32, torch.bfloat16) and PW._vox(x) % 4 == 0
                 and x.shape[1] % 2 == 0):

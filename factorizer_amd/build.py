@@ -24,7 +24,8 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
 #    lanes 48-63 on gfx950; replacing exactly those four instructions by scalar adds in the assembly restores bitwise replay,
 #    s_nop padding around them does not (tools/probes/upcat_asm_variants.py, profiles/r04_nondeterminism.md).
 #    tools/pk_opsel_audit.py counts such instructions in the built objects; tests/test_no_spills.py keeps the count at zero.
-#  * the fp32-MFMA GEMM units (gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain.hip, gemm_dw.hip): it pairs accumulator elements
+#  * the fp32-MFMA GEMM units (gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain32.hip, mlp_chain64.hip, mlp_chain_wg.hip,
+#    gemm_dw.hip): it pairs accumulator elements
 #    of DIFFERENT MFMA tiles for v_pk_* math, which needs register-to-register copies of whole accumulator tiles — +64..128 VGPRs
 #    and scratch spills in the fused epilogues (round 1);
 #  * the NMF wave programs: v_pk_fma_f32 / v_pk_mul_f32 pairs whose 64-bit register alignment costs more v_mov than the packing

@@ -21,8 +21,8 @@
 // stores 16-byte vectors (4 voxels) per register: 512 B contiguous per output row.
 //
 // This unit: the register-resident kernel (A) and the dispatcher of fz_gemm.  The persistent 32 -> 32 kernel (A') lives in
-// gemm_p32.hip, the streaming kernel (B) in gemm_stream.hip, the chained MLP kernels in mlp_chain.hip, the fused input + weight
-// gradient in gemm_dw.hip.
+// gemm_p32.hip, the streaming kernel (B) in gemm_stream.hip, the chained MLP kernels in mlp_chain32.hip, mlp_chain64.hip and
+// mlp_chain_wg.hip (host dispatch: mlp_chain.hip), the fused input + weight gradient in gemm_dw.hip.
 #include "gemm_bx.h"       // uload (brings gemm_common.h)
 #include "gemm_shared.h"   // LayerNorm-backward epilogue, knob_pos, gemm_p32_launch, chain64_lnb_launch
 

@@ -1,5 +1,6 @@
 // gemm_common.h — argument block, operand fetch and epilogue helpers shared by the channels-first GEMM
-// kernels (gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain.hip, gemm_dw.hip: fp32 MFMA family; gemm_bx.hip: split-bf16 MFMA family).
+// kernels (gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain32.hip, mlp_chain64.hip, mlp_chain_wg.hip,
+// gemm_dw.hip: fp32 MFMA family; gemm_bx.hip: split-bf16 MFMA family).
 #pragma once
 #include <cstdlib>
 

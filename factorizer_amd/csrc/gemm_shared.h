@@ -1,4 +1,5 @@
-// gemm_shared.h — what more than one unit of the fp32-MFMA GEMM family uses (gemm.hip, gemm_p32.hip, mlp_chain.hip, gemm_dw.hip):
+// gemm_shared.h — what more than one unit of the fp32-MFMA GEMM family uses (gemm.hip, gemm_p32.hip, the mlp_chain*.hip
+// units, gemm_dw.hip):
 // the LayerNorm-backward epilogue, the block-dropout arguments, the transposable-tile constants, the knob reader and the
 // launchers through which fz_gemm's dispatcher reaches gemm_p32_kernel and the chain kernels.
 #pragma once
@@ -148,7 +149,7 @@ static DropArgs drop_args(const uint32_t* m0, const uint32_t* m1, const uint32_t
 }
 static bool drop_scale_ok(const void* m, float s) { return m == nullptr || (s >= 1.f && s < 3.0e38f); }
 
-// gemm_chain_bwd_wg_kernel (mlp_chain.hip) and gemm_dw_kernel (gemm_dw.hip): accumulator of their 16x16 weight-gradient MFMAs, and
+// gemm_chain_bwd_wg_kernel (mlp_chain_wg.hip) and gemm_dw_kernel (gemm_dw.hip): accumulator of their 16x16 weight-gradient MFMAs, and
 // the row stride of the LDS tiles they turn their operands through
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTS = 66;                       // LDS row stride of the transposable tiles (floats): ≡ 2 (mod 32), even
@@ -163,7 +164,7 @@ static int knob_pos(const EnvKnob& k, int dflt) { return k.set && k.val > 0 ? k.
 template <typename AT>
 int gemm_p32_launch(const fz_gemm_desc* d, const GemmArgsT<AT>& a, fz_stream_t stream);
 
-// fz_gemm with EPI_LNBWD and M = K = 64: gemm_chain64_kernel, SINGLE form (mlp_chain.hip)
+// fz_gemm with EPI_LNBWD and M = K = 64: gemm_chain64_kernel, SINGLE form (mlp_chain64.hip)
 template <typename AT>
 int chain64_lnb_launch(const fz_gemm_desc* d, const GemmArgsT<AT>& a, fz_stream_t stream);
 

@@ -1,6 +1,6 @@
 """Dense per-voxel layers on channels-first tensors: LayerNorm over C, 1×1 GEMMs ("Linear"),
 the MLP, k2s2 (transposed) convolutions and the k3 stem — device paths over the fp32-MFMA GEMM
-family of libfactorizer_hip (csrc/gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain.hip, gemm_dw.hip, wgrad.hip, ln.hip), CPU paths composed from ATen.
+family of libfactorizer_hip (csrc/gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain32.hip, mlp_chain64.hip, mlp_chain_wg.hip, gemm_dw.hip, wgrad.hip, ln.hip), CPU paths composed from ATen.
 
 Each autograd Function below is one fused layer of the reference block:
   LNLinearFn      LayerNorm → Linear (+bias) → [ReLU]     norm.py:29-34 + linear.py:53-58 (+ factorizer.py:44)
@@ -142,7 +142,7 @@ def _ln_backward(gl, x, stats, ln_w, gadd=None):
 
 def _dgrad_lnbwd(gz, w2, x, stats, ln_w, gadd):
     """gx = LayerNormBackward(W2ᵀ·gz; x, stats, γ) + gadd and (gγ, gβ), in ONE kernel when the
-    LayerNorm width is 32, or 64 with a 64-channel gradient (csrc/gemm.hip, mlp_chain.hip EPI_LNBWD: gl never leaves the accumulators)."""
+    LayerNorm width is 32, or 64 with a 64-channel gradient (csrc/gemm.hip, mlp_chain64.hip EPI_LNBWD: gl never leaves the accumulators)."""
     B, C = x.shape[:2]
     V = _vox(x)
     Mz = gz.shape[1]
@@ -243,7 +243,7 @@ def _mlp_chain_ok(C, Hd, V):
 
 
 def _mlp_fwd_chain(x1, ln_w, ln_b, eps, w12, b1, w22, b2):
-    """x2 = x1 + fc2(gelu(fc1(LN(x1)))) in ONE kernel (csrc/mlp_chain.hip gemm_chain_kernel): the hidden
+    """x2 = x1 + fc2(gelu(fc1(LN(x1)))) in ONE kernel (csrc/mlp_chain32.hip gemm_chain_kernel): the hidden
     tensor goes from the accumulators of the first GEMM into the second; z1 (pre-activation) and
     the LayerNorm statistics are written once for the backward."""
     B, C = x1.shape[:2]
@@ -340,7 +340,7 @@ def _mlp_bwd_chain(g2, z1, w12, w22, x1, st, ln_w):
 
 
 def _mlp_wgrad_fused_ok(C, Hd, V):
-    """the chain backward that also forms dW1, db1, dW2, db2 (csrc/mlp_chain.hip gemm_chain_bwd_wg_kernel): C = 32, hidden 64
+    """the chain backward that also forms dW1, db1, dW2, db2 (csrc/mlp_chain_wg.hip gemm_chain_bwd_wg_kernel): C = 32, hidden 64
     (one launch) or 128 (one launch per 64-row half of the hidden tensor)"""
     return _mlp_chain_ok(C, Hd, V) and C == 32 and Hd in (64, 128) and os.environ.get("FZ_MLP_FUSED_WGRAD", "1") != "0"
 

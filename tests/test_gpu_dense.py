@@ -1,4 +1,5 @@
-"""-m gpu: the fp32-MFMA GEMM family (csrc/gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain.hip, gemm_dw.hip, wgrad.hip, ln.hip) behind the layer
+"""-m gpu: the fp32-MFMA GEMM family (csrc/gemm.hip, gemm_p32.hip, gemm_stream.hip, mlp_chain32.hip, mlp_chain64.hip, mlp_chain_wg.hip,
+gemm_dw.hip, wgrad.hip, ln.hip) behind the layer
 Functions of factorizer_amd/pointwise.py, against ATen on CPU (the arithmetic the reference
 runs: nn.Conv1d / nn.LayerNorm / nn.Conv3d / nn.ConvTranspose3d) and the reference goldens."""
 import pytest
@@ -311,41 +312,55 @@ def test_dice_ce_loss_fused(C):
     assert abs(ft.DiceCELoss(sigmoid=True, squared_pred=True)(zd, t.to(DEV)).item() - ld.item()) == 0.0
 
 
+@pytest.mark.parametrize("products", [_native.PRODUCTS_DEFAULT, _native.PRODUCTS_SPLIT_BF16, _native.PRODUCTS_FP32_MFMA],
+                         ids=["default", "split_bf16", "fp32_mfma"])
+@pytest.mark.parametrize("bf", [False, True])
 @pytest.mark.parametrize("C,Hd", [(32, 64), (32, 128), (64, 128)])
 @pytest.mark.parametrize("B,S", [(2, (8, 8, 8)), (1, (6, 4, 5)), (2, (16, 16, 12))])
-def test_mlp_chain_kernel(B, S, C, Hd):
-    """fz_mlp_chain (csrc/mlp_chain.hip gemm_chain_kernel) against the layer-by-layer CPU composition
-    x + fc2(gelu(fc1(LN(x)))) (factorizer.py:76, mlp.py:54-60, norm.py:29-34): forward, the saved
-    pre-activation / statistics, and the backward chain (gz1, gx1, dγ, dβ).  V = 120 and 3072 cover
-    partial column tiles."""
+def test_mlp_chain_kernel(B, S, C, Hd, bf, products):
+    """fz_mlp_chain modes 0 and 1 (csrc/mlp_chain.hip: the dispatch; mlp_chain32.hip gemm_chain_kernel, mlp_chain64.hip
+    gemm_chain64_kernel) against the layer-by-layer CPU composition x + fc2(gelu(fc1(LN(x)))) (factorizer.py:76,
+    mlp.py:54-60, norm.py:29-34): forward, the saved pre-activation / statistics, and the backward chain (gz1, gx1, dγ, dβ).
+    V = 120 and 3072 cover partial column tiles; V = 120 at C = 64 is one tile, an odd count: the 256-thread fp32-MFMA form
+    whatever the products.  Every form the dispatch can pick: fp32 and bf16 storage, each on the library's default products,
+    on split-bf16 and on fp32-MFMA products.  bf16 storage: inputs rounded first, the backward's reference reads the STORED
+    pre-activation, and each tensor written in bf16 is allowed its one stored rounding."""
     torch.manual_seed(3)
     # C = 32: hidden 64 = mlp_ratio 2 (README), 128 = mlp_ratio 4 (BraTS bundle, train.yaml:62); C = 64, hidden 128 =
     # stage 1 of the README model (gemm_chain64_kernel: the hidden tensor in two passes of 64 rows)
-    x = torch.randn(B, C, *S) * 2 + 0.5
+    rnd = (lambda t: t.bfloat16().float()) if bf else (lambda t: t)
+    x = rnd(torch.randn(B, C, *S) * 2 + 0.5)
     ln_w, ln_b = torch.rand(C) + 0.5, torch.randn(C) * 0.1
     w1, b1 = torch.randn(Hd, C) * 0.2, torch.randn(Hd) * 0.1
     w2, b2 = torch.randn(C, Hd) * 0.2, torch.randn(C) * 0.1
-    g2 = torch.randn(B, C, *S)
+    g2 = rnd(torch.randn(B, C, *S))
+    dt = torch.bfloat16 if bf else torch.float32
+    d = lambda t: t.to(DEV).contiguous()  # noqa: E731
+    xd, g2d = d(x).to(dt), d(g2).to(dt)
+    stored = dict(rtol=2.0 ** -8, why="bf16 storage: one rounding of the stored tensor") if bf else {}
+    n0 = _native.launch_count()
+    with _native.use_products(products):
+        x2, z1, st = PW._mlp_fwd_chain(xd, d(ln_w), d(ln_b), 1e-5, d(w1), d(b1), d(w2), d(b2))
+        gz1, gx1, gg, gb = PW._mlp_bwd_chain(g2d, z1, d(w1), d(w2), xd, st, d(ln_w))
+    assert _native.launch_count() > n0
+    assert x2.dtype == dt and z1.dtype == dt and gz1.dtype == dt and gx1.dtype == dt
     # CPU composition with autograd
     xc = x.clone().requires_grad_(True)
     lw, lb = ln_w.clone().requires_grad_(True), ln_b.clone().requires_grad_(True)
     xn = F.layer_norm(xc.movedim(1, -1), (C,), lw, lb, 1e-5).movedim(-1, 1)
     z1c = _lin_cpu(xn, w1.unsqueeze(-1), b1)
+    _cmp(z1.float(), z1c, "z1", **stored)
+    _cmp(x2.float(), xc + _lin_cpu(F.gelu(z1c), w2.unsqueeze(-1), b2), "x2", **stored)
+    _cmp(st[:, 0], x.mean(1).reshape(B, -1), "mean")
+    if bf:
+        # the backward reads the STORED pre-activation (bf16): give the CPU graph exactly those values (a bf16 tie
+        # broken the other way is 2^-8 of one addend)
+        z1c = z1c + (z1.float().cpu().reshape(z1c.shape) - z1c.detach())
     z1c.retain_grad()
     yc = xc + _lin_cpu(F.gelu(z1c), w2.unsqueeze(-1), b2)
     yc.backward(g2)
-    # device
-    d = lambda t: t.to(DEV).contiguous()  # noqa: E731
-    n0 = _native.launch_count()
-    x2, z1, st = PW._mlp_fwd_chain(d(x), d(ln_w), d(ln_b), 1e-5, d(w1), d(b1), d(w2), d(b2))
-    _cmp(x2, yc, "x2")
-    _cmp(z1, z1c, "z1")
-    mean = x.mean(1).reshape(B, -1)
-    _cmp(st[:, 0], mean, "mean")
-    gz1, gx1, gg, gb = PW._mlp_bwd_chain(d(g2), z1, d(w1), d(w2), d(x), st, d(ln_w))
-    assert _native.launch_count() > n0
-    _cmp(gz1, z1c.grad, "gz1")
-    _cmp(gx1, xc.grad, "gx1")
+    for n, a, r in (("gz1", gz1, z1c.grad), ("gx1", gx1, xc.grad)):
+        _cmp(a.float(), r, n, **(dict(rtol=4e-3, why=f"bf16 activation storage: {n} is rounded once on store (2^-9 relative)") if bf else {}))
     _cmp(gg, lw.grad, "dgamma")
     _cmp(gb, lb.grad, "dbeta")
 

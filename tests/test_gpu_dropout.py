@@ -302,7 +302,7 @@ def test_block_dropout_bf16_vs_masked_fp32_oracle():
 
 # ---------------------------------------------------------------- registers ------------------------------------------
 def test_dropout_kernels_do_not_spill():
-    """the kernels of csrc/dropout.hip and the dropout instantiations of csrc/mlp_chain.hip and csrc/gemm_dw.hip exist in the built objects and own no
+    """the kernels of csrc/dropout.hip and the dropout instantiations of csrc/mlp_chain32.hip and csrc/gemm_dw.hip exist in the built objects and own no
     scratch (tools/scratch_audit.py)"""
     import importlib.util
     import os
@@ -312,7 +312,7 @@ def test_dropout_kernels_do_not_spill():
     spec = importlib.util.spec_from_file_location("scratch_audit", os.path.join(root, "tools", "scratch_audit.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    ks = {name: (scratch, spills) for o in ("dropout.o", "mlp_chain.o", "gemm_dw.o") for name, scratch, spills, _v in
+    ks = {name: (scratch, spills) for o in ("dropout.o", "mlp_chain32.o", "gemm_dw.o") for name, scratch, spills, _v in
           mod.kernels_of(os.path.join(root, "factorizer_amd", "csrc", "build", o))}
     want = ["dropout_bits_kernel"] + [f"dropout_apply_kernelI{t}Li{k}E" for t in ("f", "DF16b") for k in range(3)]
     # the fused launches' dropout instantiations (one trailing DropArgs argument)

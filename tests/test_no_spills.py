@@ -11,8 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "factorizer_amd", "csrc")
 
 HOT = {
-    "mlp_chain.hip": ["gemm_chain_bwd_wg_kernelIfLi1ELi0E", "gemm_chain_bwd_wg_kernelIfLi2ELi0E", "gemm_chain_bwd_wg_kernelIfLi2ELi1E",
-                      "gemm_chain64_kernelILb0Ef", "gemm_chain64_kernelILb1Ef", "gemm_chain_kernelILb0ELi2ELi2Ef"],
+    "mlp_chain_wg.hip": ["gemm_chain_bwd_wg_kernelIfLi1ELi0E", "gemm_chain_bwd_wg_kernelIfLi2ELi0E", "gemm_chain_bwd_wg_kernelIfLi2ELi1E"],
+    "mlp_chain64.hip": ["gemm_chain64_kernelILb0Ef", "gemm_chain64_kernelILb1Ef"],
+    "mlp_chain32.hip": ["gemm_chain_kernelILb0ELi2ELi2Ef"],
     "gemm_dw.hip": ["gemm_dw_kernelILb1Ef", "gemm_dw_kernelILb0Ef"],
     "nmf_cf.hip": ["nmf_cf_bwd_tile_kernelILi1ELi1ELi4ELb0Ef", "nmf_cf_fwd_tile_kernelILi1ELi1ELi8ELb0Ef"],
     "nmf_cf_gram.hip": ["nmf_cf_bwd_gram_kernelILi4ELb0EfLi0E", "nmf_cf_bwd_gram_kernelILi4ELb0EDF16bLi2E"],
@@ -84,11 +85,12 @@ def test_no_low_from_high_packed_fp32_instruction_outside_the_exempt_units():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     res = mod.audit()
-    gemm_units = ("gemm", "gemm_p32", "gemm_stream", "mlp_chain", "gemm_dw")   # the fp32-MFMA GEMM family, one unit per kernel family
+    # the fp32-MFMA GEMM family, one unit per kernel family
+    gemm_units = ("gemm", "gemm_p32", "gemm_stream", "mlp_chain32", "mlp_chain64", "mlp_chain_wg", "gemm_dw")
     assert all(tu in res for tu in gemm_units) and "upcat" in res
-    # the disassembly really was read: the family's packed instructions sit in the chain kernels and in gemm_dw_kernel (the
-    # resident, persistent and streaming kernels hold none)
-    assert res["mlp_chain"][1] > 0 and res["gemm_dw"][1] > 0
+    # the disassembly really was read: the family's packed instructions sit in the three chain kernels and in gemm_dw_kernel
+    # (the resident, persistent and streaming kernels hold none)
+    assert all(res[tu][1] > 0 for tu in ("mlp_chain32", "mlp_chain64", "mlp_chain_wg", "gemm_dw"))
     bad = {tu: n for tu, (n, _) in res.items() if n}
     assert not bad, bad
 

@@ -18,7 +18,12 @@ struct CfGeom {
   int divisor;         // > 1: divide the result by it (last window, forward)
   float gscale_div;    // backward: gY = gather(ga) / gscale_div
   int64_t plane;       // distance between channel planes in elements (D·H·W for dense tensors)
+  int ps0, ps1, ps2;   // forward from stored factors (CF_FROM_FACTORS): the PREVIOUS window's shift, normalised to [0, S)
 };
+
+// forms of the line-coalesced forward (nmf_cf.hip): the plain read-modify-write of the running window average, and the rank-1
+// pair of a two-window SWMatricize that hands the first window over as its factors instead of as u vᵀ
+enum { CF_PLAIN = 0, CF_STORE_FACTORS = 1, CF_FROM_FACTORS = 2 };
 
 struct CfWave {
   using F = float;
@@ -267,6 +272,19 @@ __device__ __forceinline__ CfTileId cf_tile_id(const CfGeom& q, int64_t blk) {
   return id;
 }
 
+// coalesced-map chunk k of thread tid: its (row, chunk) in the tile and the TRUE coordinates of its first voxel (the window's
+// cyclic shift undone)
+template <int WPB>
+__device__ __forceinline__ void cf_chunk_voxel(const CfGeom& q, const CfTileId& id, int tid, int k, int& row, int& chunk,
+                                               int& z0, int& z1, int& z2) {
+  using TL = CfTile<WPB>;
+  const int idx = tid + k * TL::NT;
+  row = idx / TL::CHUNKS; chunk = idx % TL::CHUNKS;
+  z0 = id.g0 * 8 + (row >> 3) - q.s0; if (z0 < 0) z0 += q.D;
+  z1 = id.g1 * 8 + (row & 7) - q.s1; if (z1 < 0) z1 += q.H;
+  z2 = id.gq * WPB * 8 + chunk * 4 - q.s2; if (z2 < 0) z2 += q.W;
+}
+
 template <int WPB>
 __device__ __forceinline__ void cf_tile_decode(const CfGeom& q, const CfTileId& id, int tid, int64_t& base, int64_t& V,
                                                unsigned (&off)[2], int (&lidx)[2], unsigned (&off2)[2]) {
@@ -275,16 +293,41 @@ __device__ __forceinline__ void cf_tile_decode(const CfGeom& q, const CfTileId& 
   base = ((int64_t)id.b * q.C + (int64_t)id.hh * 8) * V;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    const int idx = tid + k * TL::NT;
-    const int row = idx / TL::CHUNKS, chunk = idx % TL::CHUNKS;
-    int z0 = id.g0 * 8 + (row >> 3) - q.s0; if (z0 < 0) z0 += q.D;
-    int z1 = id.g1 * 8 + (row & 7) - q.s1; if (z1 < 0) z1 += q.H;
-    int z2 = id.gq * WPB * 8 + chunk * 4 - q.s2; if (z2 < 0) z2 += q.W;
+    int row, chunk, z0, z1, z2;
+    cf_chunk_voxel<WPB>(q, id, tid, k, row, chunk, z0, z1, z2);
     off[k] = (unsigned)((z0 * q.H + z1) * q.W + z2);   // in-plane element offset < 2^30 (host-checked): 32 bits, so that every
     int z2b = z2 + 2; if (z2b >= q.W) z2b -= q.W;
     off2[k] = (unsigned)((z0 * q.H + z1) * q.W + z2b); // access is `uniform plane pointer (SGPR pair) + one 32-bit lane offset`
     lidx[k] = TL::at(row, chunk);
   }
+}
+
+// index (inside one (sample, head)) of the PREVIOUS window's patch that holds coalesced-map chunk k of this thread: the
+// chunk's true voxel coordinates moved by that window's shift, cyclically.  With both W-axis shifts ≡ 0 (mod 4) the four
+// voxels of a chunk lie in one patch of either window.
+template <int WPB>
+__device__ __forceinline__ unsigned cf_prev_patch(const CfGeom& q, const CfTileId& id, int tid, int k) {
+  int row, chunk, z0, z1, z2;
+  cf_chunk_voxel<WPB>(q, id, tid, k, row, chunk, z0, z1, z2);
+  z0 += q.ps0; if (z0 >= q.D) z0 -= q.D;
+  z1 += q.ps1; if (z1 >= q.H) z1 -= q.H;
+  z2 += q.ps2; if (z2 >= q.W) z2 -= q.W;
+  return (unsigned)(((z0 >> 3) * q.G1 + (z1 >> 3)) * q.G2 + (z2 >> 3));
+}
+
+// the first window's contribution to the running sum as the plain form stores it: (0.0f + fl(u·v)) — the product rounded
+// BEFORE the add (the empty asm keeps the compiler from contracting the two into an FMA, which -ffp-contract=fast allows),
+// the 0.0f turning a −0 product of the sign-free solvers into +0 — and, for bf16 storage, rounded once to bf16 as the store does
+template <typename AT>
+__device__ __forceinline__ float4 cf_first_window(float u, const float4& v) {
+  float p0 = u * v.x, p1 = u * v.y, p2 = u * v.z, p3 = u * v.w;
+  asm("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3));
+  const f32v4 f = {0.0f + p0, 0.0f + p1, 0.0f + p2, 0.0f + p3};
+  if constexpr (sizeof(AT) == 2) {
+    const f32v4 r = __builtin_convertvector(__builtin_convertvector(f, bf16v4), f32v4);
+    return make_float4(r[0], r[1], r[2], r[3]);
+  }
+  return make_float4(f[0], f[1], f[2], f[3]);
 }
 
 // owner-side LDS index of local vector jp of this lane (patch = wave)

@@ -10,6 +10,14 @@
 // the number of windows — the reference's ((0.0 + z_0) + z_1 + …) / W order (operations.py:426-433).
 // Windows are separate launches on one stream, so the accumulation is deterministic.
 //
+// Rank 1, exactly two windows, W % 64 == 0, W-axis shifts ≡ 0 (mod 4) (fz_nmf_cf_factors_supported — the README model's
+// stages 0 and 1): the first window does not write u vᵀ (one tensor) for the second to read back.  It writes its FACTORS —
+// v as a (B, heads, D, H, W) fp32 field at the true voxel positions (one eighth of t), u as 8 floats per patch — and the
+// second window rebuilds (0 + u·v) per 16-byte chunk from one float4 of v and the u of the first window's patch the chunk
+// lies in (cache resident: 1 MB at stage 0).  2 + 3 tensor passes become 1.13 + 2.13, the result keeps its bits: the product
+// is rounded before the add (cf_first_window, nmf_cf.h), bf16 storage rounds the first window's value once as the stored
+// running sum was.  Both are forms (template parameter FORM) of the line-coalesced forward kernel.
+//
 // Lane map: lane l = (p0 & 3 = l>>4, p1 = (l>>1)&7, half = l&1); for every channel dd and
 // p0-group jp the lane moves one 16-byte vector = voxels p2 = 4·half..4·half+3 of patch row
 // (p0 = 4·jp + (l>>4), p1).  Column index of local element (jp, e): n = (p0·8 + p1)·8 + 4·half + e.
@@ -18,10 +26,14 @@
 namespace fz {
 
 // One tile (WPB patches along W) of one window of the forward.
-template <int R, int SOLVER, int WPB, bool HALF, typename AT>
+// FORM (nmf_cf.h): CF_STORE_FACTORS writes the window's rank-1 factors — v as a (B, heads, D, H, W) fp32 field at the true
+// voxel positions, u as 8 floats per patch — and nothing else; CF_FROM_FACTORS rebuilds the previous window's value of every
+// voxel from them instead of reading the running sum.  Both give the bits of two CF_PLAIN launches.
+template <int R, int SOLVER, int WPB, bool HALF, typename AT, int FORM>
 __device__ __forceinline__ void cf_fwd_tile_body(const AT* __restrict__ t, const float* __restrict__ u0,
-                                                 const float* __restrict__ v0, AT* __restrict__ out, const CfGeom& q,
-                                                 const CfTileId& id, int T, float eps, float* S) {
+                                                 const float* __restrict__ v0, AT* __restrict__ out, float* vfac, float* ufac,
+                                                 const CfGeom& q, const CfTileId& id, int T, float eps, float* S) {
+  static_assert(FORM == CF_PLAIN || (R == 1 && WPB == 8 && !HALF), "the factor forms: rank 1, 8 patches per workgroup, W-axis shifts = 0 (mod 4)");
   using TL = CfTile<WPB>;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int64_t base, V;
@@ -44,6 +56,25 @@ __device__ __forceinline__ void cf_fwd_tile_body(const AT* __restrict__ t, const
   float u[8][R], v[8][R];
   nmf_forward_wave<8, 8, R, SOLVER>(w, u0, v0, x, u, v, 8, T, eps);
 
+  const int64_t bh = (int64_t)id.b * q.h + id.hh;             // (sample, head): one plane of vfac, G0·G1·G2 rows of ufac
+  const int64_t vol = (int64_t)q.D * q.H * q.W;
+  if constexpr (FORM == CF_STORE_FACTORS) {
+    // v through one plane of the exchange (the column layout of one x[dd] row), stored with the coalesced map; u (wave-uniform)
+    // by one lane
+    *reinterpret_cast<float4*>(S + own0) = make_float4(v[0][0], v[1][0], v[2][0], v[3][0]);
+    *reinterpret_cast<float4*>(S + own1) = make_float4(v[4][0], v[5][0], v[6][0], v[7][0]);
+    __syncthreads();
+    float* vp = vfac + bh * vol;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) st4(cf_at(vp, off[k]), *reinterpret_cast<const float4*>(S + lidx[k]));
+    if (lane == 0) {
+      float* up = ufac + ((((bh * q.G0 + id.g0) * q.G1 + id.g1) * q.G2 + id.gq * WPB + wave) << 3);
+      st4(up, make_float4(u[0][0], u[1][0], u[2][0], u[3][0]));
+      st4(up + 4, make_float4(u[4][0], u[5][0], u[6][0], u[7][0]));
+    }
+    return;
+  }
+
   // owner → coalesced, then the (read-modify-)write of the running window average; all loads of
   // the running sum are issued at once (one exposed round trip)
   const float dv = (float)q.divisor;
@@ -52,7 +83,20 @@ __device__ __forceinline__ void cf_fwd_tile_body(const AT* __restrict__ t, const
   // registers and every epilogue access pays a 64-bit vector address)
   asm volatile("" : "+s"(base));
   float4 old[8][2];
-  if (q.accumulate) {
+  float4 pv[2];      // CF_FROM_FACTORS: the previous window's v at this thread's two chunks,
+  float pu[2][8];    // and the u of the patch of that window each chunk lies in
+  if constexpr (FORM == CF_FROM_FACTORS) {
+    const float* vp = vfac + bh * vol;
+    const float* up = ufac + ((bh * q.G0 * q.G1 * q.G2) << 3);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      pv[k] = ld4(cf_at(vp, off[k]));
+      const float* pk = up + (cf_prev_patch<WPB>(q, id, tid, k) << 3);
+      const float4 a = ld4(pk), b = ld4(pk + 4);
+      pu[k][0] = a.x; pu[k][1] = a.y; pu[k][2] = a.z; pu[k][3] = a.w;
+      pu[k][4] = b.x; pu[k][5] = b.y; pu[k][6] = b.z; pu[k][7] = b.w;
+    }
+  } else if (q.accumulate) {
 #pragma unroll
     for (int dd = 0; dd < 8; ++dd)
 #pragma unroll
@@ -74,7 +118,10 @@ __device__ __forceinline__ void cf_fwd_tile_body(const AT* __restrict__ t, const
       for (int k = 0; k < 2; ++k) {
         const float4 z = *reinterpret_cast<const float4*>(S + c * 64 * TL::LW + lidx[k]);
         float4 o;
-        if (q.accumulate) {
+        if constexpr (FORM == CF_FROM_FACTORS) {
+          o = cf_first_window<AT>(pu[k][2 * s + c], pv[k]);
+          o.x += z.x; o.y += z.y; o.z += z.z; o.w += z.w;
+        } else if (q.accumulate) {
           o = old[2 * s + c][k];
           o.x += z.x; o.y += z.y; o.z += z.z; o.w += z.w;
         } else {
@@ -87,17 +134,18 @@ __device__ __forceinline__ void cf_fwd_tile_body(const AT* __restrict__ t, const
   }
 }
 
-template <int R, int SOLVER, int WPB, bool HALF, typename AT>
+template <int R, int SOLVER, int WPB, bool HALF, typename AT, int FORM>
 // (second launch-bounds argument = minimum WAVES PER SIMD in HIP, not workgroups per CU: 8 capped the one-patch variant
 // at 64 VGPRs — 170 spilled registers)
 // (rank 2 needs more than the 128 registers of four waves per SIMD: two — NO variant may spill to scratch, see nmf_pcf.hip)
 __global__ __launch_bounds__(WPB * 64, (WPB == 8 || R >= 2) ? 2 : 4) void nmf_cf_fwd_tile_kernel(const AT* __restrict__ t,
                                                                    const float* __restrict__ u0,
                                                                    const float* __restrict__ v0,
-                                                                   AT* __restrict__ out, CfGeom q, int T, float eps,
-                                                                   int xcd_remap) {
+                                                                   AT* __restrict__ out, float* vfac, float* ufac,
+                                                                   CfGeom q, int T, float eps, int xcd_remap) {
   extern __shared__ __attribute__((aligned(16))) float fz_lds_tile[];
-  cf_fwd_tile_body<R, SOLVER, WPB, HALF, AT>(t, u0, v0, out, q, cf_tile_id<WPB>(q, cf_logical_block(xcd_remap)), T, eps, fz_lds_tile);
+  cf_fwd_tile_body<R, SOLVER, WPB, HALF, AT, FORM>(t, u0, v0, out, vfac, ufac, q, cf_tile_id<WPB>(q, cf_logical_block(xcd_remap)), T, eps,
+                                                   fz_lds_tile);
 }
 
 // backward: gY = gather_w(ga) / W ; gt (+)= [t > 0] ∘ scatter_w(gX)
@@ -245,6 +293,7 @@ static int cf_geom(CfGeom& q, int B, int C, int D, int H, int W, const int* shif
   if (s[2] % 2) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf: W-axis shift must be even");
   q.s0 = s[0]; q.s1 = s[1]; q.s2 = s[2];
   q.accumulate = accumulate; q.divisor = divisor; q.gscale_div = 1.0f;
+  q.ps0 = q.ps1 = q.ps2 = 0;
   q.plane = (int64_t)D * H * W;
 #ifdef FZ_PROBE_PLANE_PAD   // timing probe (tools/probes/gram_floor.sh): channel planes FZ_PROBE_PLANE_PAD elements further apart
   q.plane += FZ_PROBE_PLANE_PAD;
@@ -293,9 +342,9 @@ static int cf_fwd_launch(const AT* t, const float* u0, const float* v0, AT* out,
     const unsigned nblk = (unsigned)(nmat / twpb);
 #define FZ_CF_TILE(RR, SS, WW, HH)                                                                          \
   do {                                                                                                      \
-    auto kern = nmf_cf_fwd_tile_kernel<RR, SS, WW, HH, AT>;                                                   \
+    auto kern = nmf_cf_fwd_tile_kernel<RR, SS, WW, HH, AT, CF_PLAIN>;                                         \
     const int lds = CfTile<WW>::STAGE_FLOATS * (int)sizeof(float);                                          \
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * WW), lds, st, t, u0, v0, out, q, T, eps, xr);            \
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * WW), lds, st, t, u0, v0, out, (float*)nullptr, (float*)nullptr, q, T, eps, xr); \
   } while (0)
 #define FZ_CF_TILE_W(RR, SS)                                                                                \
   do {                                                                                                      \
@@ -325,6 +374,87 @@ extern "C" int fz_nmf_cf_fwd(const void* t, const float* u0, const float* v0, vo
     return cf_fwd_launch<bf16>((const bf16*)t, u0, v0, (bf16*)out, B, C, D, H, W, shift, accumulate, divisor, R, T,
                                solver, eps, stream);
   return fail(FZ_E_ARG, "fz_nmf_cf_fwd: bad act_dtype");
+}
+
+// ---- a two-window rank-1 forward that keeps the first window as its factors ------------------------------------------
+static void cf_norm_shift(const int* shift, int D, int H, int W, int (&s)[3]) {
+  const int S[3] = {D, H, W};
+  for (int i = 0; i < 3; ++i) { s[i] = shift[i] % S[i]; if (s[i] < 0) s[i] += S[i]; }
+}
+
+extern "C" int fz_nmf_cf_factors_supported(int C, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
+                                           int nshift, const int* shifts) {
+  if (!fz_nmf_cf_supported(C, D, H, W, d, pd, ph, pw, R, T, Tgrad)) return 0;
+  if (R != 1 || nshift != 2 || !shifts || (W % 64)) return 0;
+  for (int w = 0; w < 2; ++w) {
+    int s[3];
+    cf_norm_shift(shifts + 3 * w, D, H, W, s);
+    if (s[2] % 4) return 0;
+  }
+  return 1;
+}
+
+// form: CF_STORE_FACTORS (out unused) or CF_FROM_FACTORS (prev_shift = the shift of the window that stored the factors)
+template <typename AT>
+static int cf_fwd_factors_launch(const AT* t, const float* u0, const float* v0, AT* out, float* vfac, float* ufac, int B, int C,
+                                 int D, int H, int W, const int* shift, const int* prev_shift, int form, int divisor, int R, int T,
+                                 int solver, float eps, fz_stream_t stream, const char* who) {
+  CfGeom q;
+  int rc = cf_geom(q, B, C, D, H, W, shift, form == CF_FROM_FACTORS, divisor);
+  if (rc != FZ_OK) return rc;
+  if (!t || !u0 || !v0 || !vfac || !ufac || (form == CF_FROM_FACTORS && (!out || !prev_shift))) return fail(FZ_E_ARG, who);
+  if (R != 1) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_fwd factor forms: rank 1 only");
+  if (W % 64) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_fwd factor forms: W must be a multiple of 64");
+  if (solver < FZ_SOLVER_MU || solver > FZ_SOLVER_SMU) return fail(FZ_E_ARG, "fz_nmf_cf_fwd factor forms: bad solver");
+  if (divisor < 1) return fail(FZ_E_ARG, "fz_nmf_cf_fwd factor forms: divisor < 1");
+  if (q.s2 % 4) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_fwd factor forms: W-axis shift must be a multiple of 4");
+  if (form == CF_FROM_FACTORS) {
+    int ps[3];
+    cf_norm_shift(prev_shift, D, H, W, ps);
+    if (ps[2] % 4) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_fwd factor forms: W-axis shift must be a multiple of 4");
+    q.ps0 = ps[0]; q.ps1 = ps[1]; q.ps2 = ps[2];
+  }
+  if (B == 0) return FZ_OK;
+  const int64_t nmat = (int64_t)B * q.h * q.G0 * q.G1 * q.G2;
+  if (nmat >= (int64_t)1 << 31) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf: more than 2^31 matrices");
+  const int xr = 1 | (tile_order() << 1);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nblk = (unsigned)(nmat / 8);
+  const int lds = CfTile<8>::STAGE_FLOATS * (int)sizeof(float);
+#define FZ_CF_FACT(FF, SS)                                                                                          \
+  hipLaunchKernelGGL((nmf_cf_fwd_tile_kernel<1, SS, 8, false, AT, FF>), dim3(nblk), dim3(512), lds, st, t, u0, v0, out, vfac, \
+                     ufac, q, T, eps, xr)
+  if (form == CF_STORE_FACTORS) { FZ_SOLVER_CASES(FZ_CF_FACT, CF_STORE_FACTORS); }
+  else { FZ_SOLVER_CASES(FZ_CF_FACT, CF_FROM_FACTORS); }
+  FZ_LAUNCH_CHECK();
+  return FZ_OK;
+}
+
+extern "C" int fz_nmf_cf_fwd_store_factors(const void* t, const float* u0, const float* v0, float* vfac, float* ufac, int B,
+                                           int C, int D, int H, int W, const int* shift, int R, int T, int solver, float eps,
+                                           int act_dtype, fz_stream_t stream) {
+  const char* who = "fz_nmf_cf_fwd_store_factors: null pointer (t, u0, v0, vfac or ufac)";
+  if (act_dtype == FZ_STORE_F32)
+    return cf_fwd_factors_launch<float>((const float*)t, u0, v0, nullptr, vfac, ufac, B, C, D, H, W, shift, nullptr,
+                                        CF_STORE_FACTORS, 1, R, T, solver, eps, stream, who);
+  if (act_dtype == FZ_STORE_BF16)
+    return cf_fwd_factors_launch<bf16>((const bf16*)t, u0, v0, nullptr, vfac, ufac, B, C, D, H, W, shift, nullptr,
+                                       CF_STORE_FACTORS, 1, R, T, solver, eps, stream, who);
+  return fail(FZ_E_ARG, "fz_nmf_cf_fwd_store_factors: bad act_dtype");
+}
+
+extern "C" int fz_nmf_cf_fwd_from_factors(const void* t, const float* u0, const float* v0, const float* vfac,
+                                          const float* ufac, void* out, int B, int C, int D, int H, int W, const int* shift,
+                                          const int* prev_shift, int divisor, int R, int T, int solver, float eps, int act_dtype,
+                                          fz_stream_t stream) {
+  const char* who = "fz_nmf_cf_fwd_from_factors: null pointer (t, u0, v0, vfac, ufac, out or prev_shift)";
+  if (act_dtype == FZ_STORE_F32)
+    return cf_fwd_factors_launch<float>((const float*)t, u0, v0, (float*)out, const_cast<float*>(vfac), const_cast<float*>(ufac),
+                                        B, C, D, H, W, shift, prev_shift, CF_FROM_FACTORS, divisor, R, T, solver, eps, stream, who);
+  if (act_dtype == FZ_STORE_BF16)
+    return cf_fwd_factors_launch<bf16>((const bf16*)t, u0, v0, (bf16*)out, const_cast<float*>(vfac), const_cast<float*>(ufac),
+                                       B, C, D, H, W, shift, prev_shift, CF_FROM_FACTORS, divisor, R, T, solver, eps, stream, who);
+  return fail(FZ_E_ARG, "fz_nmf_cf_fwd_from_factors: bad act_dtype");
 }
 
 template <typename AT>

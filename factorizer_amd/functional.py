@@ -97,6 +97,7 @@ class Geometry:
         self.p3 = (1,) * pad + self.patch
         self.shifts3 = [(0,) * pad + s for s in self.shifts]
         self._carr = N.shifts_array(self.shifts3)
+        self._factors_ok = {}    # nmf_cf_factors_supported, by (R, T, G)
 
     def y_shape(self, B):
         return (self.nshift * B * self.h, self.G, self.d, self.P)
@@ -375,6 +376,19 @@ def nmf_cf_supported(geo: Geometry, R, T, G) -> bool:
     return bool(N.lib().fz_nmf_cf_supported(geo.C, *geo.spatial, geo.d, *geo.patch, int(R), int(T), int(G)))
 
 
+def nmf_cf_factors_supported(geo: Geometry, R, T, G) -> bool:
+    """rank 1, two windows, W % 64 == 0, W-axis shifts multiples of 4: the forward hands window 0 to window 1 as its factors
+    (fz_nmf_cf_fwd_store_factors / fz_nmf_cf_fwd_from_factors, include/factorizer_hip.h) instead of as a stored tensor"""
+    if len(geo.spatial) != 3:
+        return False
+    k = (int(R), int(T), int(G))
+    ok = geo._factors_ok.get(k)         # the answer depends on (geometry, R, T, G) only: asked once, not per forward
+    if ok is None:
+        ok = geo._factors_ok[k] = bool(N.lib().fz_nmf_cf_factors_supported(geo.C, *geo.spatial, geo.d, *geo.patch, *k,
+                                                                          geo.nshift, geo._carr))
+    return ok
+
+
 def nmf_pcf_supported(geo: Geometry, R, T, G) -> bool:
     """the generic-patch fused core (csrc/nmf_pcf.hip): head_dim 8, <= 256 voxels per patch, any shift.  1-D and 2-D tensors
     (operations.py:318-325 is N-D generic; the reference's own test models are 2-D) run as depth-1 (and height-1) volumes:
@@ -405,20 +419,40 @@ class FactCoreFn(torch.autograd.Function):
         nb = 2 * es * t.numel()
         ad = N.act_dtype(t)
         hot = nmf_cf_supported(geo, R, T, G)      # 8x8x8 patches: csrc/nmf_cf.hip; any other patch: csrc/nmf_pcf.hip
+        key = ("nmf_cf_fwd_" if hot else "nmf_pcf_fwd_") + f"{geo.C}x" + "x".join(str(v) for v in geo.spatial)
+        st = N.stream_ptr(t)
         with _dev_guard(t):
-            for w, s in enumerate(geo.shifts3):
-                arr = (N._i * 3)(*s)
-                last = geo.nshift if w == geo.nshift - 1 else 1
-                N.set_tile_order(w & 1)       # odd windows walk the tiles backwards (_native.py: set_tile_order)
-                if hot:
-                    rc = _timed(f"nmf_cf_fwd_{geo.C}x" + "x".join(str(v) for v in geo.spatial), nb + (es * t.numel() if w else 0), cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_fwd(
-                        t.data_ptr(), u0.data_ptr(), v0.data_ptr(), out.data_ptr(), B, geo.C, *geo.spatial, arr,
-                        int(w > 0), last, R, T, N.SOLVER_ID[solver], eps, ad, N.stream_ptr(t)))
-                else:
-                    rc = _timed(f"nmf_pcf_fwd_{geo.C}x" + "x".join(str(v) for v in geo.spatial), nb + (es * t.numel() if w else 0), cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_pcf_fwd(
-                        t.data_ptr(), u0.data_ptr(), v0.data_ptr(), out.data_ptr(), B, geo.C, *geo.s3, *geo.p3, arr,
-                        int(w > 0), last, R, T, N.SOLVER_ID[solver], eps, ad, N.stream_ptr(t)))
-                N.check(rc, "fz_nmf_cf_fwd" if hot else "fz_nmf_pcf_fwd")
+            if hot and nmf_cf_factors_supported(geo, R, T, G):
+                # window 0 leaves its rank-1 factors (v: one plane per head, u: 8 floats per patch), window 1 rebuilds u vᵀ from
+                # them: 1.13 + 2.13 passes over t instead of 2 + 3, the same bits
+                vfac = torch.empty((B, geo.h, *geo.spatial), device=t.device, dtype=torch.float32)
+                ufac = torch.empty((B * geo.h * geo.G, 8), device=t.device, dtype=torch.float32)
+                s0, s1 = ((N._i * 3)(*s) for s in geo.shifts3)
+                nf = 4 * (t.numel() // 8)
+                N.set_tile_order(0)
+                rc = _timed(key, es * t.numel() + nf, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_fwd_store_factors(
+                    t.data_ptr(), u0.data_ptr(), v0.data_ptr(), vfac.data_ptr(), ufac.data_ptr(), B, geo.C, *geo.spatial, s0,
+                    R, T, N.SOLVER_ID[solver], eps, ad, st))
+                N.check(rc, "fz_nmf_cf_fwd_store_factors")
+                N.set_tile_order(1)
+                rc = _timed(key, 2 * es * t.numel() + nf, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_fwd_from_factors(
+                    t.data_ptr(), u0.data_ptr(), v0.data_ptr(), vfac.data_ptr(), ufac.data_ptr(), out.data_ptr(), B, geo.C,
+                    *geo.spatial, s1, s0, 2, R, T, N.SOLVER_ID[solver], eps, ad, st))
+                N.check(rc, "fz_nmf_cf_fwd_from_factors")
+            else:
+                for w, s in enumerate(geo.shifts3):
+                    arr = (N._i * 3)(*s)
+                    last = geo.nshift if w == geo.nshift - 1 else 1
+                    N.set_tile_order(w & 1)       # odd windows walk the tiles backwards (_native.py: set_tile_order)
+                    if hot:
+                        rc = _timed(key, nb + (es * t.numel() if w else 0), cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_fwd(
+                            t.data_ptr(), u0.data_ptr(), v0.data_ptr(), out.data_ptr(), B, geo.C, *geo.spatial, arr,
+                            int(w > 0), last, R, T, N.SOLVER_ID[solver], eps, ad, st))
+                    else:
+                        rc = _timed(key, nb + (es * t.numel() if w else 0), cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_pcf_fwd(
+                            t.data_ptr(), u0.data_ptr(), v0.data_ptr(), out.data_ptr(), B, geo.C, *geo.s3, *geo.p3, arr,
+                            int(w > 0), last, R, T, N.SOLVER_ID[solver], eps, ad, st))
+                    N.check(rc, "fz_nmf_cf_fwd" if hot else "fz_nmf_pcf_fwd")
             N.set_tile_order(0)
         ctx.save_for_backward(t, u0, v0)
         ctx.cfg = (geo, T, G, solver, eps, relu_gate)

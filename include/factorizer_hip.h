@@ -187,6 +187,28 @@ int fz_nmf_cf_bwd(const void* t, const float* u0, const float* v0, const void* g
                   int relu_gate, int R, int T, int Tgrad, int solver, float eps, int act_dtype,
                   fz_stream_t stream);
 
+/* Rank-1 forward of a TWO-window SWMatricize that hands the first window to the second as its factors, not as u vᵀ.
+ * With rank 1 the first window's output is an outer product per 8 x 512 matrix: 520 numbers standing for 4096.
+ * fz_nmf_cf_fwd_store_factors runs the first window and writes only
+ *   vfac (B, C/8, D, H, W) fp32: v of every voxel, at the voxel's TRUE position (one eighth of t),
+ *   ufac (B·C/8·(D/8)·(H/8)·(W/8), 8) fp32: u of every patch, patches in the window's own (shifted) grid order;
+ * fz_nmf_cf_fwd_from_factors runs the second (last) window, rebuilds (0 + u v) of the first from the two workspaces
+ * (prev_shift = the shift fz_nmf_cf_fwd_store_factors was called with) and writes out = ((0 + z_0) + z_1) / divisor.
+ * The pair moves 3.26 tensors where two fz_nmf_cf_fwd calls move 5, and returns the same bits: the product is rounded before
+ * the add, and for bf16 storage the first window's value is rounded to bf16 once, as the stored running sum was.
+ * fz_nmf_cf_factors_supported (shifts: HOST pointer to nshift·3 ints) is 1 only for rank 1, exactly two windows,
+ * W % 64 == 0, both W-axis shifts multiples of 4 and a geometry fz_nmf_cf_supported accepts; the launch functions return
+ * FZ_E_UNSUPPORTED / FZ_E_ARG outside it.  Everything else (rank 2, four windows, W < 64, W-axis shifts of 2) calls
+ * fz_nmf_cf_fwd once per window.  The backward is fz_nmf_cf_bwd either way: it recomputes from t. */
+int fz_nmf_cf_factors_supported(int C, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
+                                int nshift, const int* shifts);
+int fz_nmf_cf_fwd_store_factors(const void* t, const float* u0, const float* v0, float* vfac, float* ufac, int B,
+                                int C, int D, int H, int W, const int* shift, int R, int T, int solver, float eps,
+                                int act_dtype, fz_stream_t stream);
+int fz_nmf_cf_fwd_from_factors(const void* t, const float* u0, const float* v0, const float* vfac, const float* ufac,
+                               void* out, int B, int C, int D, int H, int W, const int* shift, const int* prev_shift,
+                               int divisor, int R, int T, int solver, float eps, int act_dtype, fz_stream_t stream);
+
 /* The same fused core for ANY patch (pd, ph, pw) with head_dim 8 and at most 256 voxels per patch (csrc/nmf_pcf.hip:
  * BASELINE configs[4] uses patch (5,6,5) because 160x192x160 is not divisible by 8; the p = 4 test configurations):
  * same call protocol and semantics as fz_nmf_cf_fwd / fz_nmf_cf_bwd, any shift parity. */

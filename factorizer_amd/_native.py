@@ -231,6 +231,9 @@ _SIGS.update({
     "fz_nmf_cf_factors_supported": ([_i] * 12 + [_c.POINTER(_i)], _i),
     "fz_nmf_cf_fwd_store_factors": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 3 + [_f, _i, _vp], _i),
     "fz_nmf_cf_fwd_from_factors": ([_vp] * 6 + [_i] * 5 + [_c.POINTER(_i)] * 2 + [_i] * 4 + [_f, _i, _vp], _i),
+    "fz_nmf_cf_bwd_factors_supported": ([_i] * 14 + [_c.POINTER(_i)], _i),
+    "fz_nmf_cf_bwd_store_factors": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 3 + [_f, _i, _vp], _i),
+    "fz_nmf_cf_bwd_from_factors": ([_vp] * 6 + [_i] * 5 + [_c.POINTER(_i)] * 2 + [_i] * 3 + [_f, _i, _vp], _i),
     "fz_nmf_pcf_supported": ([_i] * 11, _i),
     "fz_nmf_pcf_fwd": ([_vp] * 4 + [_i] * 8 + [_c.POINTER(_i)] + [_i] * 5 + [_f, _i, _vp], _i),
     "fz_nmf_pcf_bwd": ([_vp] * 5 + [_i] * 8 + [_c.POINTER(_i)] + [_i] * 7 + [_f, _i, _vp], _i),

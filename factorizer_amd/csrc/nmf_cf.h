@@ -18,12 +18,16 @@ struct CfGeom {
   int divisor;         // > 1: divide the result by it (last window, forward)
   float gscale_div;    // backward: gY = gather(ga) / gscale_div
   int64_t plane;       // distance between channel planes in elements (D·H·W for dense tensors)
-  int ps0, ps1, ps2;   // forward from stored factors (CF_FROM_FACTORS): the PREVIOUS window's shift, normalised to [0, S)
+  int ps0, ps1, ps2;   // from stored factors (CF_FROM_FACTORS, forward and backward): the PREVIOUS window's shift, normalised to [0, S)
 };
 
 // forms of the line-coalesced forward (nmf_cf.hip): the plain read-modify-write of the running window average, and the rank-1
-// pair of a two-window SWMatricize that hands the first window over as its factors instead of as u vᵀ
+// pair of a two-window SWMatricize that hands the first window over as its factors instead of as u vᵀ; the row-space backward
+// (nmf_cf_gram.hip) has the same three, window 0 handing over the factors of its gradient
 enum { CF_PLAIN = 0, CF_STORE_FACTORS = 1, CF_FROM_FACTORS = 2 };
+// floats of one window-0 patch in the backward pair's `cofac`: u_T[8], dL/ds[8], ga₁[8], S[8][8] — what GramBwd::row_coeffs /
+// gx_row take (352 bytes a row: 16-byte aligned)
+constexpr int CFG_COFAC = 88;
 
 struct CfWave {
   using F = float;
@@ -366,5 +370,11 @@ __device__ __forceinline__ void cf_to_owner(float* S, const int (&lidx)[2], int 
 template <typename AT>
 int cf_bwd_gram_launch(const AT* t, const float* v0, const AT* ga, AT* gt, const CfGeom& q, int64_t nmat, int T, int G,
                        float eps, int xcd_remap, hipStream_t st);
+// the two-window pair of the same kernel that hands window 0 to window 1 as the factors of its gradient (form:
+// CF_STORE_FACTORS, gt unused; CF_FROM_FACTORS, q.ps* = window 0's shift); FZ_E_UNSUPPORTED outside G = T >= 1, W % 32 == 0,
+// W-axis shifts = 0 (mod 4) and the LDS budget
+template <typename AT>
+int cf_bwd_gram_factors_launch(const AT* t, const float* v0, const AT* ga, AT* gt, float* gcfac, float* cofac, const CfGeom& q,
+                               int64_t nmat, int form, int T, int G, float eps, int xcd_remap, hipStream_t st);
 
 }  // namespace fz

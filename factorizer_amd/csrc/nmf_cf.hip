@@ -490,7 +490,8 @@ static int cf_bwd_launch(const AT* t, const float* u0, const float* v0, const AT
     // (measured, tools/probes/gram_floor.sh: both kernels sit on the tile's memory skeleton; the row-space one is 6-11 % faster
     //  everywhere except fp32 windows w > 0 of >= 2^15 matrices, where the general kernel's single late burst of
     //  running-sum reads is 3-5 % ahead: 461-464 against 478-487 us at the README's stage 0)
-    const bool gram_wins = !(sizeof(AT) == 4 && accumulate && nmat >= 32768);
+    // (probe builds: 2 = the row-space kernel wherever it applies — what the factor pair below is compared with)
+    const bool gram_wins = !(sizeof(AT) == 4 && accumulate && nmat >= 32768) || (FZ_KNOB("FZ_CF_GRAM").set && FZ_KNOB("FZ_CF_GRAM").val == 2);
     if (gram_on && gram_wins && R == 1 && solver == FZ_SOLVER_HALS && relu_gate && G >= 1) {
       rc = cf_bwd_gram_launch<AT>(t, v0, ga, gt, q, nmat, T, G, eps, xr, st);
       if (rc != FZ_E_UNSUPPORTED) return rc;
@@ -533,6 +534,75 @@ static int cf_bwd_launch(const AT* t, const float* u0, const float* v0, const AT
   else { FZ_SOLVER_CASES(FZ_CF_BWD, 2); }
   FZ_LAUNCH_CHECK();
   return FZ_OK;
+}
+
+// ---- a two-window HALS rank-1 backward behind the ReLU that keeps the first window's gradient as its factors --------
+extern "C" int fz_nmf_cf_bwd_factors_supported(int C, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
+                                               int solver, int relu_gate, int nshift, const int* shifts) {
+  if (FZ_KNOB("FZ_CF_BWD_FACTORS").set && FZ_KNOB("FZ_CF_BWD_FACTORS").val == 0) return 0;   // probe builds: 0 = the plain launches
+  if (!fz_nmf_cf_factors_supported(C, D, H, W, d, pd, ph, pw, R, T, Tgrad, nshift, shifts)) return 0;
+  if (solver != FZ_SOLVER_HALS || !relu_gate) return 0;
+  if (T < 1 || Tgrad < T) return 0;           // 1 <= G = T: v_start is v0.  G < T: a per-patch vector, the plain launches
+  if ((C / 8) * (int64_t)(D / 8) * (H / 8) * (W / 8) >= ((int64_t)1 << 31)) return 0;   // cofac rows of one sample
+  const int lds = (CfTile<4>::STAGE_FLOATS + 4 * gram_hist_floats(T - 1) + 4 * 8 * CFG_COFAC) * (int)sizeof(float);
+  return lds <= 64 * 1024 ? 1 : 0;
+}
+
+template <typename AT>
+static int cf_bwd_factors_launch(const AT* t, const float* v0, const AT* ga, AT* gt, float* gcfac, float* cofac, int B, int C,
+                                 int D, int H, int W, const int* shift, const int* prev_shift, int form, int nshift, int T,
+                                 int Tgrad, float eps, fz_stream_t stream, const char* who) {
+  CfGeom q;
+  int rc = cf_geom(q, B, C, D, H, W, shift, form == CF_FROM_FACTORS, 1);
+  if (rc != FZ_OK) return rc;
+  if (!t || !v0 || !ga || !gcfac || !cofac || (form == CF_FROM_FACTORS && (!gt || !prev_shift))) return fail(FZ_E_ARG, who);
+  if (W % 64) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_bwd factor forms: W must be a multiple of 64");
+  if (nshift != 2) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_bwd factor forms: exactly two windows");
+  if (T < 1 || Tgrad < T) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_bwd factor forms: every iteration graded (1 <= T <= Tgrad)");
+  if (q.s2 % 4) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_bwd factor forms: W-axis shift must be a multiple of 4");
+  if (form == CF_FROM_FACTORS) {
+    int ps[3];
+    cf_norm_shift(prev_shift, D, H, W, ps);
+    if (ps[2] % 4) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_bwd factor forms: W-axis shift must be a multiple of 4");
+    q.ps0 = ps[0]; q.ps1 = ps[1]; q.ps2 = ps[2];
+  }
+  if (B == 0) return FZ_OK;
+  q.gscale_div = (float)nshift;
+  const int64_t nmat = (int64_t)B * q.h * q.G0 * q.G1 * q.G2;
+  if (nmat >= (int64_t)1 << 31) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf: more than 2^31 matrices");
+  const int xr = 1 | (tile_order() << 1);
+  rc = cf_bwd_gram_factors_launch<AT>(t, v0, ga, gt, gcfac, cofac, q, nmat, form, T, T, eps, xr, (hipStream_t)stream);
+  if (rc == FZ_E_UNSUPPORTED) return fail(rc, "fz_nmf_cf_bwd factor forms: history exceeds the LDS budget");
+  return rc;
+}
+
+extern "C" int fz_nmf_cf_bwd_store_factors(const void* t, const float* v0, const void* ga, float* gcfac, float* cofac, int B,
+                                           int C, int D, int H, int W, const int* shift, int nshift, int T, int Tgrad,
+                                           float eps, int act_dtype, fz_stream_t stream) {
+  const char* who = "fz_nmf_cf_bwd_store_factors: null pointer (t, v0, ga, gcfac or cofac)";
+  if (act_dtype == FZ_STORE_F32)
+    return cf_bwd_factors_launch<float>((const float*)t, v0, (const float*)ga, nullptr, gcfac, cofac, B, C, D, H, W, shift,
+                                        nullptr, CF_STORE_FACTORS, nshift, T, Tgrad, eps, stream, who);
+  if (act_dtype == FZ_STORE_BF16)
+    return cf_bwd_factors_launch<bf16>((const bf16*)t, v0, (const bf16*)ga, nullptr, gcfac, cofac, B, C, D, H, W, shift,
+                                       nullptr, CF_STORE_FACTORS, nshift, T, Tgrad, eps, stream, who);
+  return fail(FZ_E_ARG, "fz_nmf_cf_bwd_store_factors: bad act_dtype");
+}
+
+extern "C" int fz_nmf_cf_bwd_from_factors(const void* t, const float* v0, const void* ga, const float* gcfac,
+                                          const float* cofac, void* gt, int B, int C, int D, int H, int W, const int* shift,
+                                          const int* prev_shift, int nshift, int T, int Tgrad, float eps, int act_dtype,
+                                          fz_stream_t stream) {
+  const char* who = "fz_nmf_cf_bwd_from_factors: null pointer (t, v0, ga, gcfac, cofac, gt or prev_shift)";
+  if (act_dtype == FZ_STORE_F32)
+    return cf_bwd_factors_launch<float>((const float*)t, v0, (const float*)ga, (float*)gt, const_cast<float*>(gcfac),
+                                        const_cast<float*>(cofac), B, C, D, H, W, shift, prev_shift, CF_FROM_FACTORS, nshift, T,
+                                        Tgrad, eps, stream, who);
+  if (act_dtype == FZ_STORE_BF16)
+    return cf_bwd_factors_launch<bf16>((const bf16*)t, v0, (const bf16*)ga, (bf16*)gt, const_cast<float*>(gcfac),
+                                       const_cast<float*>(cofac), B, C, D, H, W, shift, prev_shift, CF_FROM_FACTORS, nshift, T,
+                                       Tgrad, eps, stream, who);
+  return fail(FZ_E_ARG, "fz_nmf_cf_bwd_from_factors: bad act_dtype");
 }
 
 extern "C" int fz_nmf_cf_bwd(const void* t, const float* u0, const float* v0, const void* ga, void* gt, int B,

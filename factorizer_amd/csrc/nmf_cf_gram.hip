@@ -56,126 +56,52 @@ __device__ __forceinline__ float4 cf_raw_f4(const uint2& v) {
                      __uint_as_float(v.y & 0xffff0000u));
 }
 
+// The first window's gated gradient as the plain form leaves it in gt for the second: for bf16 storage rounded once to bf16,
+// as the store does
+template <typename AT>
+__device__ __forceinline__ float cf_as_stored(float v) {
+  if constexpr (sizeof(AT) == 2) {
+    const f32v4 f = {v, v, v, v};
+    const f32v4 r = __builtin_convertvector(__builtin_convertvector(f, bf16v4), f32v4);
+    return r[0];
+  }
+  return v;
+}
+
+// One tile (WPB patches along W) of one window.
+// FORM (nmf_cf.h), for the two-window pair that hands window 0 to window 1 in factored form (dL/dX of the row-space reverse
+// mode IS factored: u_T gcᵀ + gs·1ᵀ + ga₁ v_startᵀ + S X, and X is the t that window 1 loads anyway):
+//   CF_STORE_FACTORS  window 0 stops in front of the output stage and writes gc — gcfac (B, heads, D, H, W) fp32, at the
+//                     true voxel positions, through one plane of the exchange — and the 88 coefficients of its patch
+//                     (cofac, the window's own grid order); gt is not touched;
+//   CF_FROM_FACTORS   window 1 does not read gt: every lane rebuilds window 0's gated value of its 2 x 4 columns with
+//                     gram_gx_elem — the function gx_row evaluates — from gcfac (coalesced load, exchange), the coefficients
+//                     of the window-0 patch each 16-byte chunk lies in (the <= 8 patches a window-1 patch overlaps, staged in
+//                     wave-private LDS) and its resident X, and adds it to its own gated row in front of the exchange.
+//                     v_start is v0 (G = T), looked up at the chunk's column inside the window-0 patch.
+// Both W-axis shifts are multiples of 4 (!HALF), so a chunk lies in one patch of either window.  The pair returns the bits of
+// two CF_PLAIN launches (accumulate 0, then 1): same coefficients, same expression, the same two-operand add.
+// The body is nmf_cf_gram_body.inc, included by the plain kernel and by the kernel of the two factor forms.
 template <int WPB, bool HALF, typename AT, int MODE>
 __global__ __launch_bounds__(WPB * 64, WPB == 4 ? FZ_GRAM_WAVES : 1) void nmf_cf_bwd_gram_kernel(
     const AT* __restrict__ t, const float* __restrict__ v0, const AT* __restrict__ ga, AT* __restrict__ gt, CfGeom q,
     int T, int G, float eps, int xcd_remap) {
   extern __shared__ __attribute__((aligned(16))) float fz_lds_cfg[];
-  using TL = CfTile<WPB>;
-  using Raw = typename CfRaw<AT>::T;
-  constexpr int NB = MODE == CFG_RAW ? 8 : 4;            // channels per register batch
-  constexpr int IMG = 64 * TL::LW;                      // floats of one channel image
-  float* S = fz_lds_cfg;
-  const CfTileId id = cf_tile_id<WPB>(q, cf_logical_block(xcd_remap));
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int64_t base, V;
-  unsigned off[2], off2[2];
-  int lidx[2];
-  cf_tile_decode<WPB>(q, id, tid, base, V, off, lidx, off2);
-  const int own0 = cf_owner_lidx<WPB>(lane, wave, 0), own1 = cf_owner_lidx<WPB>(lane, wave, 1);
-  float* hist = S + TL::STAGE_FLOATS + wave * gram_hist_floats(G - 1);
+  constexpr int FORM = CF_PLAIN;
+  float* const gcfac = nullptr;
+  float* const cofac = nullptr;
+#include "nmf_cf_gram_body.inc"
+}
 
-  float x[8][8];
-#pragma unroll
-  for (int dd = 0; dd < 8; ++dd)
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float4 v = cf_ld4<HALF>(t + base + dd * V, off[k], off2[k]);
-      x[dd][k * 4 + 0] = v.x; x[dd][k * 4 + 1] = v.y; x[dd][k * 4 + 2] = v.z; x[dd][k * 4 + 3] = v.w;
-    }
-  cf_to_owner<WPB>(S, lidx, own0, own1, x);
-
-  CfWave w{lane};
-  GramBwd<8, CfWave> P;
-  Raw gq[NB][2];
-  auto request_g = [&]() {
-#pragma unroll
-    for (int dd = 0; dd < NB; ++dd)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) gq[dd][k] = cf_ld_raw<HALF>(ga + base + dd * V, off[k], off2[k]);
-  };
-#ifdef FZ_PROBE_GRAM_NOMATH   // timing probe (tools/probes/gram_floor.sh): loads, exchanges and stores only
-  float probe_acc = 0.f;
-  request_g();
-#else
-  P.forward(w, x, v0, 8, 512, T, G, eps, hist, request_g);
-#endif
-  asm volatile("" : "+s"(base));
-  // dL/da: coalesced -> owner through the stage, two rows at a time, consumed at once
-#pragma unroll
-  for (int bt = 0; bt < 8 / NB; ++bt) {
-#pragma unroll
-    for (int s = 0; s < NB / 2; ++s) {
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) *reinterpret_cast<float4*>(S + c * IMG + lidx[k]) = cf_raw_f4(gq[2 * s + c][k]);
-      if (MODE == CFG_HALVES && bt == 0 && s == NB / 2 - 1) {
-#pragma unroll
-        for (int dd = 0; dd < NB; ++dd)
-#pragma unroll
-          for (int k = 0; k < 2; ++k) gq[dd][k] = cf_ld_raw<HALF>(ga + base + (NB + dd) * V, off[k], off2[k]);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const float4 a0 = *reinterpret_cast<const float4*>(S + c * IMG + own0);
-        const float4 a1 = *reinterpret_cast<const float4*>(S + c * IMG + own1);
-        const float grow[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        FZ_GRAM_OUT_ROW(NB * bt + 2 * s + c, grow);
-      }
-      __syncthreads();
-    }
-  }
-  // The running sum of the earlier windows is requested stage by stage, right in front of the rows it is added to
-  // (requested earlier — by DMA when dL/da has been consumed, or inside the reverse sweep — window 1 took 10-25 us longer)
-#ifdef FZ_PROBE_GRAM_NOMATH
-#else
-  P.reverse(w, x, 1.0f / q.gscale_div, [] {});
-#endif
-#pragma unroll
-  for (int bt = 0; bt < 8 / NB; ++bt) {
-#pragma unroll
-    for (int s = 0; s < NB / 2; ++s) {
-      Raw old[2][2];
-      if (q.accumulate) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-          for (int k = 0; k < 2; ++k) old[c][k] = cf_ld_raw<HALF>(gt + base + (NB * bt + 2 * s + c) * V, off[k], off2[k]);
-      }
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int m = NB * bt + 2 * s + c;
-        float o[8];
-#ifdef FZ_PROBE_GRAM_NOMATH
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = x[m][e] + probe_acc;
-#else
-        float srow[8], gsm, ga1m;
-        P.row_coeffs(w, m, srow, gsm, ga1m);
-        P.gx_row(m, x, srow, gsm, ga1m, o);
-#endif
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = x[m][e] > 0.f ? o[e] : 0.f;
-        *reinterpret_cast<float4*>(S + c * IMG + own0) = make_float4(o[0], o[1], o[2], o[3]);
-        *reinterpret_cast<float4*>(S + c * IMG + own1) = make_float4(o[4], o[5], o[6], o[7]);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          float4 z = *reinterpret_cast<const float4*>(S + c * IMG + lidx[k]);
-          if (q.accumulate) {
-            const float4 o = cf_raw_f4(old[c][k]);
-            z.x += o.x; z.y += o.y; z.z += o.z; z.w += o.w;
-          }
-          cf_st4<HALF>(gt + base + (NB * bt + 2 * s + c) * V, off[k], off2[k], z);
-        }
-      __syncthreads();
-    }
-  }
+// the factor forms (FORM = CF_STORE_FACTORS: gt unused; CF_FROM_FACTORS: q.ps* = window 0's shift)
+template <typename AT, int MODE, int FORM>
+__global__ __launch_bounds__(256, FZ_GRAM_WAVES) void nmf_cf_bwd_gram_fac_kernel(
+    const AT* __restrict__ t, const float* __restrict__ v0, const AT* __restrict__ ga, AT* __restrict__ gt,
+    float* __restrict__ gcfac, float* __restrict__ cofac, CfGeom q, int T, int G, float eps, int xcd_remap) {
+  extern __shared__ __attribute__((aligned(16))) float fz_lds_cfg[];
+  constexpr int WPB = 4;
+  constexpr bool HALF = false;
+#include "nmf_cf_gram_body.inc"
 }
 
 template <typename AT>
@@ -216,6 +142,27 @@ int cf_bwd_gram_launch(const AT* t, const float* v0, const AT* ga, AT* gt, const
   FZ_LAUNCH_CHECK();
   return FZ_OK;
 }
+template <typename AT>
+int cf_bwd_gram_factors_launch(const AT* t, const float* v0, const AT* ga, AT* gt, float* gcfac, float* cofac, const CfGeom& q,
+                               int64_t nmat, int form, int T, int G, float eps, int xcd_remap, hipStream_t st) {
+  if ((q.s2 % 4) || (q.ps2 % 4) || (q.G2 % 4) || G != T || G < 1) return FZ_E_UNSUPPORTED;
+  int glds = (CfTile<4>::STAGE_FLOATS + 4 * gram_hist_floats(G - 1)) * (int)sizeof(float);
+  if (form == CF_FROM_FACTORS) glds += 4 * 8 * CFG_COFAC * (int)sizeof(float);
+  if (glds > 64 * 1024) return FZ_E_UNSUPPORTED;
+  const unsigned nblk = (unsigned)(nmat / 4);
+  constexpr int kRegMode = sizeof(AT) == 4 ? CFG_HALVES : CFG_RAW;
+  if (form == CF_STORE_FACTORS)
+    hipLaunchKernelGGL((nmf_cf_bwd_gram_fac_kernel<AT, kRegMode, CF_STORE_FACTORS>), dim3(nblk), dim3(256), glds, st, t, v0, ga,
+                       gt, gcfac, cofac, q, T, G, eps, xcd_remap);
+  else
+    hipLaunchKernelGGL((nmf_cf_bwd_gram_fac_kernel<AT, kRegMode, CF_FROM_FACTORS>), dim3(nblk), dim3(256), glds, st, t, v0, ga,
+                       gt, gcfac, cofac, q, T, G, eps, xcd_remap);
+  FZ_LAUNCH_CHECK();
+  return FZ_OK;
+}
+template int cf_bwd_gram_factors_launch<float>(const float*, const float*, const float*, float*, float*, float*, const CfGeom&, int64_t, int, int, int, float, int, hipStream_t);
+template int cf_bwd_gram_factors_launch<bf16>(const bf16*, const float*, const bf16*, bf16*, float*, float*, const CfGeom&, int64_t, int, int, int, float, int, hipStream_t);
+
 template int cf_bwd_gram_launch<float>(const float*, const float*, const float*, float*, const CfGeom&, int64_t, int, int, float, int, hipStream_t);
 template int cf_bwd_gram_launch<bf16>(const bf16*, const float*, const bf16*, bf16*, const CfGeom&, int64_t, int, int, float, int, hipStream_t);
 

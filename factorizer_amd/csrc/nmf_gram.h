@@ -28,6 +28,20 @@ namespace fz {
 // (64 floats of scratch for the one-time re-ordering of K, then 12 per step: u (8), rho, nb, q)
 FZ_HD int gram_hist_floats(int steps) { return 64 + (steps > 0 ? steps : 0) * 12; }
 
+// Column j of one row of dL/dX (ungated) from that row's coefficients: uTm = u_T[m], gsm = dL/ds_m, ga1m = ga₁[m],
+// srow[k] = S[m][k]; gcj, vsj = dL/dc and v_start of the column.  GramBwd::gx_row evaluates it on its own state, the
+// from-factors form of the fused core's backward (nmf_cf_gram.hip) on the coefficients another launch stored — ONE
+// expression, so that both round (and contract) alike and the rebuilt value has the bits of the computed one.
+template <class F, int NPL>
+FZ_HD F gram_gx_elem(const F& uTm, const F& gcj, const F& gsm, const F& ga1m, const F& vsj, const F (&srow)[8],
+                     const F (&x)[8][NPL], int j) {
+  F acc = uTm * gcj + gsm;
+  acc = acc + ga1m * vsj;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) acc = acc + srow[k] * x[k][j];
+  return acc;
+}
+
 template <int NPL, class W>
 struct GramBwd {
   using F = typename W::F;
@@ -261,13 +275,7 @@ struct GramBwd {
   }
   FZ_HD void gx_row(int m, const F (&x)[8][NPL], const F (&srow)[8], const F& gsm, const F& ga1m, F (&out)[NPL]) const {
 #pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-      F acc = uT[m] * gc[j] + gsm;
-      acc = acc + ga1m * vs[j];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) acc = acc + srow[k] * x[k][j];
-      out[j] = acc;
-    }
+    for (int j = 0; j < NPL; ++j) out[j] = gram_gx_elem<F, NPL>(uT[m], gc[j], gsm, ga1m, vs[j], srow, x, j);
   }
 };
 

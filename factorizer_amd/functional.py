@@ -389,6 +389,20 @@ def nmf_cf_factors_supported(geo: Geometry, R, T, G) -> bool:
     return ok
 
 
+def nmf_cf_bwd_factors_supported(geo: Geometry, R, T, G, solver, relu_gate) -> bool:
+    """where nmf_cf_factors_supported holds, for HALS behind the ReLU with every iteration graded (G = T): the backward hands
+    window 0's gradient to window 1 as its factors (fz_nmf_cf_bwd_store_factors / fz_nmf_cf_bwd_from_factors,
+    include/factorizer_hip.h) instead of as a stored tensor"""
+    if len(geo.spatial) != 3:
+        return False
+    k = ("bwd", int(R), int(T), int(G), solver, bool(relu_gate))
+    ok = geo._factors_ok.get(k)         # asked once per (geometry, R, T, G, solver, gate), not per backward
+    if ok is None:
+        ok = geo._factors_ok[k] = bool(N.lib().fz_nmf_cf_bwd_factors_supported(
+            geo.C, *geo.spatial, geo.d, *geo.patch, *k[1:4], N.SOLVER_ID[solver], int(k[5]), geo.nshift, geo._carr))
+    return ok
+
+
 def nmf_pcf_supported(geo: Geometry, R, T, G) -> bool:
     """the generic-patch fused core (csrc/nmf_pcf.hip): head_dim 8, <= 256 voxels per patch, any shift.  1-D and 2-D tensors
     (operations.py:318-325 is N-D generic; the reference's own test models are 2-D) run as depth-1 (and height-1) volumes:
@@ -475,6 +489,27 @@ class FactCoreFn(torch.autograd.Function):
         ad = N.act_dtype(t)
         hot = nmf_cf_supported(geo, R, T, G)
         with _dev_guard(t):
+            if hot and nmf_cf_bwd_factors_supported(geo, R, T, G, solver, relu_gate):
+                # window 0 leaves the factors of its gradient (gc: one plane per head, 88 coefficients per patch), window 1
+                # rebuilds the gated value from them and its own t: 2.15 + 3.15 passes over t instead of 3 + 4
+                gcfac = torch.empty((B, geo.h, *geo.spatial), device=t.device, dtype=torch.float32)
+                cofac = torch.empty((B * geo.h * geo.G, 88), device=t.device, dtype=torch.float32)
+                s0, s1 = ((N._i * 3)(*s) for s in geo.shifts3)
+                key = f"nmf_cf_bwd_{geo.C}x" + "x".join(str(v) for v in geo.spatial)
+                nf = 4 * (t.numel() // 8) + 4 * cofac.numel()
+                st = N.stream_ptr(t)
+                N.set_tile_order(0)
+                rc = _timed(key, 2 * es * t.numel() + nf, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_bwd_store_factors(
+                    t.data_ptr(), v0.data_ptr(), ga.data_ptr(), gcfac.data_ptr(), cofac.data_ptr(), B, geo.C, *geo.spatial, s0,
+                    geo.nshift, T, G, eps, ad, st))
+                N.check(rc, "fz_nmf_cf_bwd_store_factors")
+                N.set_tile_order(1)
+                rc = _timed(key, 3 * es * t.numel() + nf, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_bwd_from_factors(
+                    t.data_ptr(), v0.data_ptr(), ga.data_ptr(), gcfac.data_ptr(), cofac.data_ptr(), gt.data_ptr(), B, geo.C,
+                    *geo.spatial, s1, s0, geo.nshift, T, G, eps, ad, st))
+                N.check(rc, "fz_nmf_cf_bwd_from_factors")
+                N.set_tile_order(0)
+                return (gt,) + (None,) * 8
             for w, s in enumerate(geo.shifts3):
                 arr = (N._i * 3)(*s)
                 N.set_tile_order(w & 1)

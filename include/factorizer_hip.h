@@ -199,7 +199,7 @@ int fz_nmf_cf_bwd(const void* t, const float* u0, const float* v0, const void* g
  * fz_nmf_cf_factors_supported (shifts: HOST pointer to nshift·3 ints) is 1 only for rank 1, exactly two windows,
  * W % 64 == 0, both W-axis shifts multiples of 4 and a geometry fz_nmf_cf_supported accepts; the launch functions return
  * FZ_E_UNSUPPORTED / FZ_E_ARG outside it.  Everything else (rank 2, four windows, W < 64, W-axis shifts of 2) calls
- * fz_nmf_cf_fwd once per window.  The backward is fz_nmf_cf_bwd either way: it recomputes from t. */
+ * fz_nmf_cf_fwd once per window.  The backward recomputes from t either way (fz_nmf_cf_bwd, or the pair below). */
 int fz_nmf_cf_factors_supported(int C, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
                                 int nshift, const int* shifts);
 int fz_nmf_cf_fwd_store_factors(const void* t, const float* u0, const float* v0, float* vfac, float* ufac, int B,
@@ -208,6 +208,34 @@ int fz_nmf_cf_fwd_store_factors(const void* t, const float* u0, const float* v0,
 int fz_nmf_cf_fwd_from_factors(const void* t, const float* u0, const float* v0, const float* vfac, const float* ufac,
                                void* out, int B, int C, int D, int H, int W, const int* shift, const int* prev_shift,
                                int divisor, int R, int T, int solver, float eps, int act_dtype, fz_stream_t stream);
+
+/* HALS rank-1 backward behind the ReLU (relu_gate = 1) of a TWO-window SWMatricize that hands the first window's gradient
+ * to the second in factored form, not as a tensor.  The row-space reverse mode (csrc/nmf_gram.h) produces a window's
+ * dL/dt per 8 x 512 matrix as u_T gcᵀ + gs 1ᵀ + ga1 v0ᵀ + S t: one value gc per voxel and 88 coefficients per patch.
+ * fz_nmf_cf_bwd_store_factors runs the first window and writes only
+ *   gcfac (B, C/8, D, H, W) fp32: gc of every voxel, at the voxel's TRUE position (one eighth of t),
+ *   cofac (B·C/8·(D/8)·(H/8)·(W/8), 88) fp32: u_T[8], gs[8], ga1[8], S[8][8] of every patch, patches in the window's own
+ *         (shifted) grid order;
+ * fz_nmf_cf_bwd_from_factors runs the second (last) window, rebuilds the first window's gated gradient of every voxel from
+ * the two workspaces and the t it holds anyway (prev_shift = the shift fz_nmf_cf_bwd_store_factors was called with) and
+ * writes gt = g_0 + g_1 without reading gt.  The pair moves 5.3 tensors where two fz_nmf_cf_bwd calls move 7, and returns
+ * the bits of two row-space launches: the same coefficients go through the same expression, and for bf16 storage the first
+ * window's value is rounded to bf16 once, as the stored tensor was.  (fz_nmf_cf_bwd itself takes the general kernel for an
+ * accumulating fp32 window of 2^15 or more matrices; against that kernel the pair agrees to rounding, not to the bit.)
+ * fz_nmf_cf_bwd_factors_supported (shifts: HOST pointer to nshift·3 ints) is 1 only where fz_nmf_cf_factors_supported is
+ * (rank 1, exactly two windows, W % 64 == 0, both W-axis shifts multiples of 4) and the solver is FZ_SOLVER_HALS,
+ * relu_gate = 1, every iteration is graded (1 <= T <= Tgrad: v_start is then v0) and one sample has fewer than 2^31 patches
+ * (the predicate takes no B: the launch functions enforce the total, B·C/8·(D/8)·(H/8)·(W/8) cofac rows < 2^31);
+ * the launch functions return FZ_E_UNSUPPORTED / FZ_E_ARG outside what they can see of it (they take no rank, solver or
+ * gate: rank 1, HALS, relu_gate = 1 are what they compute).  Everything else calls fz_nmf_cf_bwd once per window. */
+int fz_nmf_cf_bwd_factors_supported(int C, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
+                                    int solver, int relu_gate, int nshift, const int* shifts);
+int fz_nmf_cf_bwd_store_factors(const void* t, const float* v0, const void* ga, float* gcfac, float* cofac, int B, int C,
+                                int D, int H, int W, const int* shift, int nshift, int T, int Tgrad, float eps,
+                                int act_dtype, fz_stream_t stream);
+int fz_nmf_cf_bwd_from_factors(const void* t, const float* v0, const void* ga, const float* gcfac, const float* cofac,
+                               void* gt, int B, int C, int D, int H, int W, const int* shift, const int* prev_shift,
+                               int nshift, int T, int Tgrad, float eps, int act_dtype, fz_stream_t stream);
 
 /* The same fused core for ANY patch (pd, ph, pw) with head_dim 8 and at most 256 voxels per patch (csrc/nmf_pcf.hip:
  * BASELINE configs[4] uses patch (5,6,5) because 160x192x160 is not divisible by 8; the p = 4 test configurations):

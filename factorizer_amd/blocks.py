@@ -115,7 +115,7 @@ class FactorizerBlock(nn.Module):
 
     def _core_cfg(self):
         """(grad steps, solver id) if matricize→NMF→inverse can run as the fused channels-first
-        kernels (SWMatricize head_dim 8, patch 8³ — csrc/nmf_cf.hip — or any patch of ≤ 256 voxels — csrc/nmf_pcf.hip;
+        kernels (SWMatricize head_dim 8, patch 8³ — csrc/nmf_cf_fwd.hip, csrc/nmf_cf_bwd.hip — or any patch of ≤ 256 voxels — csrc/nmf_pcf.hip;
         native MU/HALS, rank ≤ 2), else None."""
         f = self.fact
         mf = f.factorize

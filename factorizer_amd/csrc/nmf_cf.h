@@ -1,5 +1,6 @@
-// nmf_cf.h — declarations shared by the translation units of the fused FactMixer core (nmf_cf.hip, nmf_cf_gram.hip):
-// geometry, the per-wave policy of the NMF programs, the line-coalesced tile map and its LDS exchange.
+// nmf_cf.h — what the translation units of the fused FactMixer core share (nmf_cf.hip: argument checks and the entry points;
+// nmf_cf_fwd.hip, nmf_cf_bwd.hip, nmf_cf_gram.hip: one kernel family and its launcher each): geometry, the per-wave policy of
+// the NMF programs, the line-coalesced tile map and its LDS exchange, the launchers and their argument block.
 #pragma once
 #include <cstdlib>
 
@@ -21,7 +22,7 @@ struct CfGeom {
   int ps0, ps1, ps2;   // from stored factors (CF_FROM_FACTORS, forward and backward): the PREVIOUS window's shift, normalised to [0, S)
 };
 
-// forms of the line-coalesced forward (nmf_cf.hip): the plain read-modify-write of the running window average, and the rank-1
+// forms of the line-coalesced forward (nmf_cf_fwd.hip): the plain read-modify-write of the running window average, and the rank-1
 // pair of a two-window SWMatricize that hands the first window over as its factors instead of as u vᵀ; the row-space backward
 // (nmf_cf_gram.hip) has the same three, window 0 handing over the factors of its gradient
 enum { CF_PLAIN = 0, CF_STORE_FACTORS = 1, CF_FROM_FACTORS = 2 };
@@ -82,7 +83,7 @@ struct CfAddr {
   int64_t V;
 };
 
-__device__ __forceinline__ bool cf_decode(const CfGeom& q, int64_t mat, int lane, CfAddr& a) {
+__device__ __forceinline__ void cf_decode(const CfGeom& q, int64_t mat, int lane, CfAddr& a) {
   unsigned t = (unsigned)mat;  // the host rejects > 2^31 matrices
   const int g2 = (int)(t % (unsigned)q.G2); t /= (unsigned)q.G2;
   const int g1 = (int)(t % (unsigned)q.G1); t /= (unsigned)q.G1;
@@ -99,7 +100,6 @@ __device__ __forceinline__ bool cf_decode(const CfGeom& q, int64_t mat, int lane
     int z0 = g0 * 8 + jp * 4 + (lane >> 4) - q.s0; if (z0 < 0) z0 += q.D;
     a.off[jp] = ((int64_t)z0 * q.H + z1) * q.W + z2;
   }
-  return true;
 }
 
 // AT = storage type of the channels-first tensors t / out / ga / gt (float or bf16); the wave program
@@ -158,46 +158,13 @@ __device__ __forceinline__ int64_t cf_logical_block(int xcd_remap) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
 }
 
-template <int R, int SOLVER, typename AT>
-__global__ __launch_bounds__(1024) void nmf_cf_fwd_kernel(const AT* __restrict__ t, const float* __restrict__ u0,
-                                                          const float* __restrict__ v0, AT* __restrict__ out,
-                                                          CfGeom q, int64_t nmat, int T, float eps, int xcd_remap) {
-  const int lane = threadIdx.x & 63;
-  const int64_t mat = cf_logical_block(xcd_remap) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (mat >= nmat) return;
-  CfWave w{lane};
-  CfAddr a;
-  cf_decode(q, mat, lane, a);
-  float x[8][8], u[8][R], v[8][R];
-  cf_load(t, a, x);
-  nmf_forward_wave<8, 8, R, SOLVER>(w, u0, v0, x, u, v, 8, T, eps);
-  const float dv = (float)q.divisor;
-  const bool dv_pow2 = cf_pow2(dv);
-#pragma unroll
-  for (int dd = 0; dd < 8; ++dd)
-#pragma unroll
-    for (int jp = 0; jp < 2; ++jp) {
-      AT* p = out + a.base + dd * a.V + a.off[jp];
-      float4 o;
-      if (q.accumulate) {
-        o = ld4(p);
-        o.x += x[dd][jp * 4 + 0]; o.y += x[dd][jp * 4 + 1]; o.z += x[dd][jp * 4 + 2]; o.w += x[dd][jp * 4 + 3];
-      } else {
-        o = make_float4(0.0f + x[dd][jp * 4 + 0], 0.0f + x[dd][jp * 4 + 1], 0.0f + x[dd][jp * 4 + 2],
-                        0.0f + x[dd][jp * 4 + 3]);
-      }
-      if (q.divisor > 1) o = cf_divide4(o, dv, dv_pow2);
-      st4(p, o);
-    }
-}
-
 // ---- line-coalesced variant -----------------------------------------------------------------------
 // A workgroup owns WPB patches that are neighbours along W, i.e. for every (channel, p0, p1) one
 // contiguous run of WPB·8 floats.  Global memory is touched only with the COALESCED map
 //   thread → (row = (p0, p1), 16-byte chunk of the run)      [whole 128-B lines per request]
 // and the patch-owner map of CfWave is reached through an LDS exchange, two channels per stage
-// (the 64 data registers are reused in place).  The direct kernel above touches 32 lines per load
-// instruction and uses 32 B of each; this one touches 1/4 as many, fully.
+// (the 64 data registers are reused in place).  The direct-gather kernels touch 32 lines per load
+// instruction and use 32 B of each; this one touches 1/4 as many, fully.
 //
 // LDS image of one channel: 64 rows (p0, p1) of CHUNKS 16-byte chunks.  Four access patterns touch it — coalesced-map
 // writes and owner-map reads on the way in, owner-map writes and coalesced-map reads on the way out — and the hardware
@@ -365,16 +332,32 @@ __device__ __forceinline__ void cf_to_owner(float* S, const int (&lidx)[2], int 
 }
 
 
+// ---- the launchers: the entry points (nmf_cf.hip) have checked the arguments and filled the argument block ----
+struct CfLaunch {
+  CfGeom q;
+  int64_t nmat;     // matrices (patches x heads x samples) of the window, < 2^31
+  int xr;           // cf_logical_block's word: bit 0 the XCD remap, bit 1 the thread's tile order
+  hipStream_t st;
+};
+
+// one window of the forward (nmf_cf_fwd.hip).  form CF_PLAIN: vfac = ufac = null; the factor forms: rank 1, W % 64 == 0 and
+// W-axis shifts = 0 (mod 4) (checked by the caller), CF_STORE_FACTORS leaves out unused, CF_FROM_FACTORS reads q.ps*
+template <typename AT>
+int cf_fwd_launch(const AT* t, const float* u0, const float* v0, AT* out, float* vfac, float* ufac, const CfLaunch& a, int form,
+                  int R, int T, int solver, float eps);
+// one window of the backward (nmf_cf_bwd.hip): the row-space kernel where it applies and wins, else the general kernels
+template <typename AT>
+int cf_bwd_launch(const AT* t, const float* u0, const float* v0, const AT* ga, AT* gt, const CfLaunch& a, int relu_gate, int R,
+                  int T, int G, int solver, float eps);
 // row-space reverse mode for HALS rank 1 behind a ReLU (nmf_cf_gram.hip); returns FZ_E_UNSUPPORTED when the launch does
 // not fit its LDS budget (the caller then takes the general kernels)
 template <typename AT>
-int cf_bwd_gram_launch(const AT* t, const float* v0, const AT* ga, AT* gt, const CfGeom& q, int64_t nmat, int T, int G,
-                       float eps, int xcd_remap, hipStream_t st);
+int cf_bwd_gram_launch(const AT* t, const float* v0, const AT* ga, AT* gt, const CfLaunch& a, int T, int G, float eps);
 // the two-window pair of the same kernel that hands window 0 to window 1 as the factors of its gradient (form:
 // CF_STORE_FACTORS, gt unused; CF_FROM_FACTORS, q.ps* = window 0's shift); FZ_E_UNSUPPORTED outside G = T >= 1, W % 32 == 0,
 // W-axis shifts = 0 (mod 4) and the LDS budget
 template <typename AT>
-int cf_bwd_gram_factors_launch(const AT* t, const float* v0, const AT* ga, AT* gt, float* gcfac, float* cofac, const CfGeom& q,
-                               int64_t nmat, int form, int T, int G, float eps, int xcd_remap, hipStream_t st);
+int cf_bwd_gram_factors_launch(const AT* t, const float* v0, const AT* ga, AT* gt, float* gcfac, float* cofac, const CfLaunch& a,
+                               int form, int T, int G, float eps);
 
 }  // namespace fz

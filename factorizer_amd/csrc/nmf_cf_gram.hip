@@ -6,7 +6,7 @@
 // 2 450 instead of 3 600 vector instructions per matrix and no per-column history in LDS (12.7 KB per wave in the general
 // kernel: two workgroups per CU).  dL/dY is consumed row by row as it comes out of the exchange, dL/dX is produced row by
 // row into it — neither ever occupies 64 registers next to X: <= 168 registers, three workgroups of four waves per CU.
-// Same tile / exchange / store scheme as cf_bwd_tile_body (nmf_cf.hip).
+// Same tile / exchange / store scheme as cf_bwd_tile_body (nmf_cf_bwd.hip).
 //
 // What the launch is bound by (tools/probes/gram_floor.sh, profiles/r05_gram_floor.md): with the arithmetic compiled out
 // (-DFZ_PROBE_GRAM_NOMATH: loads, exchanges, stores) it takes 345-357 us for window 0 and 485-493 us for window 1 at stage
@@ -105,8 +105,8 @@ __global__ __launch_bounds__(256, FZ_GRAM_WAVES) void nmf_cf_bwd_gram_fac_kernel
 }
 
 template <typename AT>
-int cf_bwd_gram_launch(const AT* t, const float* v0, const AT* ga, AT* gt, const CfGeom& q, int64_t nmat, int T, int G,
-                       float eps, int xcd_remap, hipStream_t st) {
+int cf_bwd_gram_launch(const AT* t, const float* v0, const AT* ga, AT* gt, const CfLaunch& a, int T, int G, float eps) {
+  const CfGeom& q = a.q;
   const bool half = (q.s2 % 4) != 0;
 #ifdef FZ_PROBE_GRAM_WPB   // timing probe (tools/probes/gram_tile.sh): FZ_PROBE_GRAM_WPB patches along W per workgroup instead of 4
   const int twpb = (q.G2 % FZ_PROBE_GRAM_WPB) == 0 ? FZ_PROBE_GRAM_WPB : ((q.G2 % 4) == 0 ? 4 : 1);
@@ -123,9 +123,9 @@ int cf_bwd_gram_launch(const AT* t, const float* v0, const AT* ga, AT* gt, const
 #ifndef FZ_PROBE_GRAM_WPB
   if (glds > 64 * 1024) return FZ_E_UNSUPPORTED;
 #endif
-  const unsigned nblk = (unsigned)(nmat / twpb);
+  const unsigned nblk = (unsigned)(a.nmat / twpb);
 #define FZ_CF_BWD_GRAM(WW, HH, MM) \
-  hipLaunchKernelGGL((nmf_cf_bwd_gram_kernel<WW, HH, AT, MM>), dim3(nblk), dim3(64 * WW), glds, st, t, v0, ga, gt, q, T, G, eps, xcd_remap)
+  hipLaunchKernelGGL((nmf_cf_bwd_gram_kernel<WW, HH, AT, MM>), dim3(nblk), dim3(64 * WW), glds, a.st, t, v0, ga, gt, q, T, G, eps, a.xr)
   constexpr int kRegMode = kF32 ? CFG_HALVES : CFG_RAW;
 #ifdef FZ_PROBE_GRAM_WPB
   if (!half && twpb == FZ_PROBE_GRAM_WPB) {
@@ -143,27 +143,28 @@ int cf_bwd_gram_launch(const AT* t, const float* v0, const AT* ga, AT* gt, const
   return FZ_OK;
 }
 template <typename AT>
-int cf_bwd_gram_factors_launch(const AT* t, const float* v0, const AT* ga, AT* gt, float* gcfac, float* cofac, const CfGeom& q,
-                               int64_t nmat, int form, int T, int G, float eps, int xcd_remap, hipStream_t st) {
+int cf_bwd_gram_factors_launch(const AT* t, const float* v0, const AT* ga, AT* gt, float* gcfac, float* cofac, const CfLaunch& a,
+                               int form, int T, int G, float eps) {
+  const CfGeom& q = a.q;
   if ((q.s2 % 4) || (q.ps2 % 4) || (q.G2 % 4) || G != T || G < 1) return FZ_E_UNSUPPORTED;
   int glds = (CfTile<4>::STAGE_FLOATS + 4 * gram_hist_floats(G - 1)) * (int)sizeof(float);
   if (form == CF_FROM_FACTORS) glds += 4 * 8 * CFG_COFAC * (int)sizeof(float);
   if (glds > 64 * 1024) return FZ_E_UNSUPPORTED;
-  const unsigned nblk = (unsigned)(nmat / 4);
+  const unsigned nblk = (unsigned)(a.nmat / 4);
   constexpr int kRegMode = sizeof(AT) == 4 ? CFG_HALVES : CFG_RAW;
   if (form == CF_STORE_FACTORS)
-    hipLaunchKernelGGL((nmf_cf_bwd_gram_fac_kernel<AT, kRegMode, CF_STORE_FACTORS>), dim3(nblk), dim3(256), glds, st, t, v0, ga,
-                       gt, gcfac, cofac, q, T, G, eps, xcd_remap);
+    hipLaunchKernelGGL((nmf_cf_bwd_gram_fac_kernel<AT, kRegMode, CF_STORE_FACTORS>), dim3(nblk), dim3(256), glds, a.st, t, v0, ga,
+                       gt, gcfac, cofac, q, T, G, eps, a.xr);
   else
-    hipLaunchKernelGGL((nmf_cf_bwd_gram_fac_kernel<AT, kRegMode, CF_FROM_FACTORS>), dim3(nblk), dim3(256), glds, st, t, v0, ga,
-                       gt, gcfac, cofac, q, T, G, eps, xcd_remap);
+    hipLaunchKernelGGL((nmf_cf_bwd_gram_fac_kernel<AT, kRegMode, CF_FROM_FACTORS>), dim3(nblk), dim3(256), glds, a.st, t, v0, ga,
+                       gt, gcfac, cofac, q, T, G, eps, a.xr);
   FZ_LAUNCH_CHECK();
   return FZ_OK;
 }
-template int cf_bwd_gram_factors_launch<float>(const float*, const float*, const float*, float*, float*, float*, const CfGeom&, int64_t, int, int, int, float, int, hipStream_t);
-template int cf_bwd_gram_factors_launch<bf16>(const bf16*, const float*, const bf16*, bf16*, float*, float*, const CfGeom&, int64_t, int, int, int, float, int, hipStream_t);
+template int cf_bwd_gram_factors_launch<float>(const float*, const float*, const float*, float*, float*, float*, const CfLaunch&, int, int, int, float);
+template int cf_bwd_gram_factors_launch<bf16>(const bf16*, const float*, const bf16*, bf16*, float*, float*, const CfLaunch&, int, int, int, float);
 
-template int cf_bwd_gram_launch<float>(const float*, const float*, const float*, float*, const CfGeom&, int64_t, int, int, float, int, hipStream_t);
-template int cf_bwd_gram_launch<bf16>(const bf16*, const float*, const bf16*, bf16*, const CfGeom&, int64_t, int, int, float, int, hipStream_t);
+template int cf_bwd_gram_launch<float>(const float*, const float*, const float*, float*, const CfLaunch&, int, int, float);
+template int cf_bwd_gram_launch<bf16>(const bf16*, const float*, const bf16*, bf16*, const CfLaunch&, int, int, float);
 
 }  // namespace fz

@@ -46,7 +46,7 @@ struct DevWave {
   // kernels: the distributed form is the same arithmetic per row but the compiler contracts / schedules the 1-row and the
   // 8-row code differently (results differ in the last bit: 4e-7 relative on y, tools/probes/nmf_ab.py), and
   // tests/test_gpu_parity.py::test_nmf_8x512_vs_oracle[3-mu] sits on its 1e-4 bound for one of 65 536 matrices (2.0e-4
-  // with the distributed form).  These kernels are off the hot path; the fused cores (nmf_cf.hip, nmf_pcf.hip), whose
+  // with the distributed form).  These kernels are off the hot path; the fused cores (nmf_cf_fwd.hip, nmf_cf_bwd.hip, nmf_pcf.hip), whose
   // rank-2 forms are VALU-bound, use it.
 #ifndef FZ_DIST_ROWS
 #define FZ_DIST_ROWS 0

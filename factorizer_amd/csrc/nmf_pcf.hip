@@ -1,5 +1,5 @@
 // nmf_pcf.hip — FactMixer core on channels-first tensors for ANY patch size with head_dim 8 and at most 256 voxels
-// per patch: shifted-window matricize → NMF → inverse matricize in one kernel per window, like nmf_cf.hip (which keeps
+// per patch: shifted-window matricize → NMF → inverse matricize in one kernel per window, like nmf_cf_fwd.hip (which keeps
 // the 8x8x8 hot shape and its line-coalesced exchange).
 //
 // Replaces SWMatricize.forward → NMF.forward → SWMatricize.inverse_forward (factorizer/factorizer.py:41-50;

@@ -370,7 +370,7 @@ def gnmf_decompose(x, u0, v0, T, G, solver, eps=1e-16):
 
 # ---- fused FactMixer core on channels-first tensors ------------------------------------------
 def nmf_cf_supported(geo: Geometry, R, T, G) -> bool:
-    """the 8x8x8 hot-shape kernels (csrc/nmf_cf.hip)"""
+    """the 8x8x8 hot-shape kernels (csrc/nmf_cf_fwd.hip, csrc/nmf_cf_bwd.hip, csrc/nmf_cf_gram.hip; asked of csrc/nmf_cf.hip)"""
     if len(geo.spatial) != 3 or any(s[2] % 2 for s in geo.shifts):  # odd W-axis shifts, 1-D / 2-D: the generic-patch kernels
         return False
     return bool(N.lib().fz_nmf_cf_supported(geo.C, *geo.spatial, geo.d, *geo.patch, int(R), int(T), int(G)))
@@ -416,9 +416,22 @@ def nmf_core_supported(geo: Geometry, R, T, G) -> bool:
     return nmf_cf_supported(geo, R, T, G) or nmf_pcf_supported(geo, R, T, G)
 
 
+def _core_launches(t, geo: Geometry, ad):
+    """What the launches of one FactCoreFn call share, computed once.  launch(name, key, nbytes, *args) runs the library's
+    `name` under the KernelTimer and checks its status; the storage dtype and t's stream close every argument list of the
+    family.  With it: the geometry suffix of the timer keys and the windows' shifts as ctypes arrays."""
+    lib, cols, tail = N.lib(), t.numel() // geo.C, (ad, N.stream_ptr(t))
+
+    def launch(name, key, nbytes, *args):
+        fn = getattr(lib, name)
+        N.check(_timed(key, nbytes, cols=cols, fn=lambda: fn(*args, *tail)), name)
+
+    return launch, f"{geo.C}x" + "x".join(str(v) for v in geo.spatial), [(N._i * 3)(*s) for s in geo.shifts3]
+
+
 class FactCoreFn(torch.autograd.Function):
     """a = SWMatricize⁻¹(NMF(SWMatricize(t))) for t >= 0 already activated (factorizer.py:41-50)
-    without materialising the matricized tensors (csrc/nmf_cf.hip).  `relu_gate`: the caller's
+    without materialising the matricized tensors (csrc/nmf_cf_fwd.hip, csrc/nmf_cf_bwd.hip).  `relu_gate`: the caller's
     t is relu(z) (so t >= 0 — the library relies on it: HALS rank 1 then runs its backward in the row space,
     csrc/nmf_gram.h); the backward returns the gradient w.r.t. z (gated by [t > 0])."""
 
@@ -429,44 +442,32 @@ class FactCoreFn(torch.autograd.Function):
         B = t.shape[0]
         out = torch.empty_like(t)
         R = u0.shape[1]
-        es = t.element_size()
-        nb = 2 * es * t.numel()
-        ad = N.act_dtype(t)
+        nt = t.element_size() * t.numel()         # bytes of one pass over t
         hot = nmf_cf_supported(geo, R, T, G)      # 8x8x8 patches: csrc/nmf_cf.hip; any other patch: csrc/nmf_pcf.hip
-        key = ("nmf_cf_fwd_" if hot else "nmf_pcf_fwd_") + f"{geo.C}x" + "x".join(str(v) for v in geo.spatial)
-        st = N.stream_ptr(t)
+        launch, sp, shifts = _core_launches(t, geo, N.act_dtype(t))
+        key = ("nmf_cf_fwd_" if hot else "nmf_pcf_fwd_") + sp
+        lead = (t.data_ptr(), u0.data_ptr(), v0.data_ptr())
+        dims = (B, geo.C, *geo.spatial) if hot else (B, geo.C, *geo.s3, *geo.p3)
+        cfg = (R, T, N.SOLVER_ID[solver], eps)
         with _dev_guard(t):
             if hot and nmf_cf_factors_supported(geo, R, T, G):
                 # window 0 leaves its rank-1 factors (v: one plane per head, u: 8 floats per patch), window 1 rebuilds u vᵀ from
                 # them: 1.13 + 2.13 passes over t instead of 2 + 3, the same bits
                 vfac = torch.empty((B, geo.h, *geo.spatial), device=t.device, dtype=torch.float32)
                 ufac = torch.empty((B * geo.h * geo.G, 8), device=t.device, dtype=torch.float32)
-                s0, s1 = ((N._i * 3)(*s) for s in geo.shifts3)
+                fac = (vfac.data_ptr(), ufac.data_ptr())
                 nf = 4 * (t.numel() // 8)
                 N.set_tile_order(0)
-                rc = _timed(key, es * t.numel() + nf, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_fwd_store_factors(
-                    t.data_ptr(), u0.data_ptr(), v0.data_ptr(), vfac.data_ptr(), ufac.data_ptr(), B, geo.C, *geo.spatial, s0,
-                    R, T, N.SOLVER_ID[solver], eps, ad, st))
-                N.check(rc, "fz_nmf_cf_fwd_store_factors")
+                launch("fz_nmf_cf_fwd_store_factors", key, nt + nf, *lead, *fac, *dims, shifts[0], *cfg)
                 N.set_tile_order(1)
-                rc = _timed(key, 2 * es * t.numel() + nf, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_fwd_from_factors(
-                    t.data_ptr(), u0.data_ptr(), v0.data_ptr(), vfac.data_ptr(), ufac.data_ptr(), out.data_ptr(), B, geo.C,
-                    *geo.spatial, s1, s0, 2, R, T, N.SOLVER_ID[solver], eps, ad, st))
-                N.check(rc, "fz_nmf_cf_fwd_from_factors")
+                launch("fz_nmf_cf_fwd_from_factors", key, 2 * nt + nf, *lead, *fac, out.data_ptr(), *dims, shifts[1], shifts[0], 2,
+                       *cfg)
             else:
-                for w, s in enumerate(geo.shifts3):
-                    arr = (N._i * 3)(*s)
-                    last = geo.nshift if w == geo.nshift - 1 else 1
+                name = "fz_nmf_cf_fwd" if hot else "fz_nmf_pcf_fwd"
+                for w, arr in enumerate(shifts):
                     N.set_tile_order(w & 1)       # odd windows walk the tiles backwards (_native.py: set_tile_order)
-                    if hot:
-                        rc = _timed(key, nb + (es * t.numel() if w else 0), cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_fwd(
-                            t.data_ptr(), u0.data_ptr(), v0.data_ptr(), out.data_ptr(), B, geo.C, *geo.spatial, arr,
-                            int(w > 0), last, R, T, N.SOLVER_ID[solver], eps, ad, st))
-                    else:
-                        rc = _timed(key, nb + (es * t.numel() if w else 0), cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_pcf_fwd(
-                            t.data_ptr(), u0.data_ptr(), v0.data_ptr(), out.data_ptr(), B, geo.C, *geo.s3, *geo.p3, arr,
-                            int(w > 0), last, R, T, N.SOLVER_ID[solver], eps, ad, st))
-                    N.check(rc, "fz_nmf_cf_fwd" if hot else "fz_nmf_pcf_fwd")
+                    launch(name, key, (3 if w else 2) * nt, *lead, out.data_ptr(), *dims, arr, int(w > 0),
+                           geo.nshift if w == geo.nshift - 1 else 1, *cfg)
             N.set_tile_order(0)
         ctx.save_for_backward(t, u0, v0)
         ctx.cfg = (geo, T, G, solver, eps, relu_gate)
@@ -484,58 +485,39 @@ class FactCoreFn(torch.autograd.Function):
         gt = torch.empty_like(t)
         B = t.shape[0]
         R = u0.shape[1]
-        es = t.element_size()
-        nb = 3 * es * t.numel()
+        nt = t.element_size() * t.numel()
         ad = N.act_dtype(t)
         hot = nmf_cf_supported(geo, R, T, G)
+        launch, sp, shifts = _core_launches(t, geo, ad)
+        key = ("nmf_cf_bwd_" if hot else "nmf_pcf_bwd_") + sp
+        dims = (B, geo.C, *geo.spatial) if hot else (B, geo.C, *geo.s3, *geo.p3)
         with _dev_guard(t):
             if hot and nmf_cf_bwd_factors_supported(geo, R, T, G, solver, relu_gate):
                 # window 0 leaves the factors of its gradient (gc: one plane per head, 88 coefficients per patch), window 1
                 # rebuilds the gated value from them and its own t: 2.15 + 3.15 passes over t instead of 3 + 4
                 gcfac = torch.empty((B, geo.h, *geo.spatial), device=t.device, dtype=torch.float32)
                 cofac = torch.empty((B * geo.h * geo.G, 88), device=t.device, dtype=torch.float32)
-                s0, s1 = ((N._i * 3)(*s) for s in geo.shifts3)
-                key = f"nmf_cf_bwd_{geo.C}x" + "x".join(str(v) for v in geo.spatial)
+                lead = (t.data_ptr(), v0.data_ptr(), ga.data_ptr(), gcfac.data_ptr(), cofac.data_ptr())
+                cfg = (geo.nshift, T, G, eps)
                 nf = 4 * (t.numel() // 8) + 4 * cofac.numel()
-                st = N.stream_ptr(t)
                 N.set_tile_order(0)
-                rc = _timed(key, 2 * es * t.numel() + nf, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_bwd_store_factors(
-                    t.data_ptr(), v0.data_ptr(), ga.data_ptr(), gcfac.data_ptr(), cofac.data_ptr(), B, geo.C, *geo.spatial, s0,
-                    geo.nshift, T, G, eps, ad, st))
-                N.check(rc, "fz_nmf_cf_bwd_store_factors")
+                launch("fz_nmf_cf_bwd_store_factors", key, 2 * nt + nf, *lead, *dims, shifts[0], *cfg)
                 N.set_tile_order(1)
-                rc = _timed(key, 3 * es * t.numel() + nf, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_bwd_from_factors(
-                    t.data_ptr(), v0.data_ptr(), ga.data_ptr(), gcfac.data_ptr(), cofac.data_ptr(), gt.data_ptr(), B, geo.C,
-                    *geo.spatial, s1, s0, geo.nshift, T, G, eps, ad, st))
-                N.check(rc, "fz_nmf_cf_bwd_from_factors")
-                N.set_tile_order(0)
-                return (gt,) + (None,) * 8
-            for w, s in enumerate(geo.shifts3):
-                arr = (N._i * 3)(*s)
-                N.set_tile_order(w & 1)
-                if hot:
-                    rc = _timed(f"nmf_cf_bwd_{geo.C}x" + "x".join(str(v) for v in geo.spatial), nb + (es * t.numel() if w else 0), cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_cf_bwd(
-                        t.data_ptr(), u0.data_ptr(), v0.data_ptr(), ga.data_ptr(), gt.data_ptr(), B, geo.C,
-                        *geo.spatial, arr, int(w > 0), geo.nshift, int(relu_gate), R, T, G, N.SOLVER_ID[solver], eps,
-                        ad, N.stream_ptr(t)))
-                elif w > 0 and N.lib().fz_nmf_pcf_bwd_prefers_separate(*geo.p3, ad):
-                    # the window's gradient into its own buffer, then one coalesced add (include/factorizer_hip.h)
-                    tmp = torch.empty_like(gt)
-                    rc = _timed(f"nmf_pcf_bwd_{geo.C}x" + "x".join(str(v) for v in geo.spatial), nb, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_pcf_bwd(
-                        t.data_ptr(), u0.data_ptr(), v0.data_ptr(), ga.data_ptr(), tmp.data_ptr(), B, geo.C,
-                        *geo.s3, *geo.p3, arr, 0, geo.nshift, int(relu_gate), R, T, G, N.SOLVER_ID[solver], eps,
-                        ad, N.stream_ptr(t)))
-                    N.check(rc, "fz_nmf_pcf_bwd")
-                    rc = _timed(f"window_add_{geo.C}x" + "x".join(str(v) for v in geo.spatial), nb, cols=t.numel() // geo.C, fn=lambda: N.lib().fz_act_add(
-                        gt.data_ptr(), tmp.data_ptr(), gt.numel(), ad, N.stream_ptr(t)))
-                    N.check(rc, "fz_act_add")
-                    del tmp
-                else:
-                    rc = _timed(f"nmf_pcf_bwd_{geo.C}x" + "x".join(str(v) for v in geo.spatial), nb + (es * t.numel() if w else 0), cols=t.numel() // geo.C, fn=lambda: N.lib().fz_nmf_pcf_bwd(
-                        t.data_ptr(), u0.data_ptr(), v0.data_ptr(), ga.data_ptr(), gt.data_ptr(), B, geo.C,
-                        *geo.s3, *geo.p3, arr, int(w > 0), geo.nshift, int(relu_gate), R, T, G, N.SOLVER_ID[solver], eps,
-                        ad, N.stream_ptr(t)))
-                N.check(rc, "fz_nmf_cf_bwd" if hot else "fz_nmf_pcf_bwd")
+                launch("fz_nmf_cf_bwd_from_factors", key, 3 * nt + nf, *lead, gt.data_ptr(), *dims, shifts[1], shifts[0], *cfg)
+            else:
+                name = "fz_nmf_cf_bwd" if hot else "fz_nmf_pcf_bwd"
+                lead = (t.data_ptr(), u0.data_ptr(), v0.data_ptr(), ga.data_ptr())
+                cfg = (geo.nshift, int(relu_gate), R, T, G, N.SOLVER_ID[solver], eps)
+                for w, arr in enumerate(shifts):
+                    N.set_tile_order(w & 1)
+                    if not hot and w > 0 and N.lib().fz_nmf_pcf_bwd_prefers_separate(*geo.p3, ad):
+                        # the window's gradient into its own buffer, then one coalesced add (include/factorizer_hip.h)
+                        tmp = torch.empty_like(gt)
+                        launch(name, key, 3 * nt, *lead, tmp.data_ptr(), *dims, arr, 0, *cfg)
+                        launch("fz_act_add", "window_add_" + sp, 3 * nt, gt.data_ptr(), tmp.data_ptr(), gt.numel())
+                        del tmp
+                    else:
+                        launch(name, key, (4 if w else 3) * nt, *lead, gt.data_ptr(), *dims, arr, int(w > 0), *cfg)
             N.set_tile_order(0)
         return (gt,) + (None,) * 8
 

@@ -1491,7 +1491,7 @@ class FactorizerBlockFn(torch.autograd.Function):
     hand-chained backward: both residual-gradient additions are fused into the LayerNorm-backward
     kernels (`gadd`), nothing but the tensors listed in `save_for_backward` survives the forward.
 
-    core = matricize → NMF → inverse: the fused channels-first kernels (csrc/nmf_cf.hip) when
+    core = matricize → NMF → inverse: the fused channels-first kernels (csrc/nmf_cf_fwd.hip, csrc/nmf_cf_bwd.hip) when
     `cfg["core"]`, else the native modular chain swm_fwd → nmf → swm_inv."""
 
     _fz_acts = (0, 4, 5, 14, 15, 16, 17, 18)   # inputs that are activations (see _param_sinks_ok); every other input is a parameter

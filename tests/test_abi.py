@@ -71,6 +71,19 @@ def test_host_side_argument_checks(built_lib):
     assert rc == -4 and b"act_dtype" in lib.fz_last_error_string()
 
 
+def test_fused_core_history_limit(built_lib):
+    """fz_nmf_cf_supported sizes the backward's per-wave history (Hist<8, 8, R>::floats(G), csrc/nmf_core.h) against 160 KB of
+    LDS: rank 1 fits up to T = G = 76 (162 896 bytes; 77: 165 012), rank 2 up to 37 (161 040; 38: 165 280)."""
+    from factorizer_amd import _native
+    lib = _native.lib()
+
+    def ok(R, T):
+        return lib.fz_nmf_cf_supported(8, 8, 8, 8, 8, 8, 8, 8, R, T, T)
+
+    assert ok(1, 76) == 1 and ok(1, 77) == 0
+    assert ok(2, 37) == 1 and ok(2, 38) == 0
+
+
 def test_fused_chain_and_finish_queue_argument_checks(built_lib):
     """Round-5 entry points: which shapes take the out-projection in front of the MLP chain, what the descriptor must carry, and
     the finish queue's host-side state — all decided before anything touches the device."""

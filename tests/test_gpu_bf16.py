@@ -199,7 +199,7 @@ def test_swm_and_nmf_bf16_storage():
 
 
 def test_fused_core_bf16_matches_modular_bf16():
-    """csrc/nmf_cf.hip with bf16 loads/stores against the fp32 oracle on the rounded input (window 0 is stored in
+    """csrc/nmf_cf_fwd.hip / nmf_cf_bwd.hip with bf16 loads/stores against the fp32 oracle on the rounded input (window 0 is stored in
     bf16 before window 1 is added: 2 roundings forward)."""
     torch.manual_seed(6)
     C, S = 16, (8, 16, 64)

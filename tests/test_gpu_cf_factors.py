@@ -1,5 +1,5 @@
 """-m gpu: the two-window rank-1 forward of the fused FactMixer core that hands the first window to the second as its
-factors (csrc/nmf_cf.hip: fz_nmf_cf_fwd_store_factors / fz_nmf_cf_fwd_from_factors) against the two fz_nmf_cf_fwd launches it
+factors (csrc/nmf_cf_fwd.hip; entry points in csrc/nmf_cf.hip: fz_nmf_cf_fwd_store_factors / fz_nmf_cf_fwd_from_factors) against the two fz_nmf_cf_fwd launches it
 replaces — bit for bit, the issue's contract — and once against the CPU oracle's restatement of the reference chain
 SWMatricize.forward -> NMF(rank 1) -> SWMatricize.inverse_forward (factorizer.py:41-50; operations.py:417-434)."""
 import pytest

@@ -1,6 +1,6 @@
 """-m gpu: the native cd and smu solvers (csrc/nmf_core.h SOLVER_CD / SOLVER_SMU) in every wave-program kernel family — the
 standalone ft.NMF kernels (nmf_r*_cdsmu.hip), the split-N kernels for wide matrices (nmf_global.hip), the 8^3 fused core
-(nmf_cf.hip) and the generic-patch fused core (nmf_pcf.hip) — against the reference's goldens (g8, g11) and the package's composed
+(nmf_cf_fwd.hip, nmf_cf_bwd.hip) and the generic-patch fused core (nmf_pcf.hip) — against the reference's goldens (g8, g11) and the package's composed
 path in float64.  Every test asserts that native kernels ran."""
 import copy
 import re

@@ -367,7 +367,7 @@ def test_block_cfg2_full_size_runs():
 @pytest.mark.parametrize("shifts", [None, [None, 4, (4, 0, 4), (0, 4, 0)], [None], [None, 2, 4, 6], [(2, 6, 2), (5, 3, 6)]])
 @pytest.mark.parametrize("solver,R", [("hals", 1), ("mu", 2), ("hals", 2)])
 def test_fact_core_fused_vs_modular(S, shifts, solver, R):
-    """csrc/nmf_cf.hip (gather → NMF → scatter/average per window) against the modular chain
+    """csrc/nmf_cf_fwd.hip / nmf_cf_bwd.hip (gather → NMF → scatter/average per window) against the modular chain
     SWMatricize → NMF → inverse (itself checked against the reference goldens).  W = 24: direct
     gather kernels (3 patches along W); W = 64 / 32: line-coalesced kernels with 8 / 4 patches per
     workgroup; W-axis shifts 2 and 6 (the BraTS bundle's windows, train.yaml:50-54) move as 8-byte

@@ -15,7 +15,8 @@ HOT = {
     "mlp_chain64.hip": ["gemm_chain64_kernelILb0Ef", "gemm_chain64_kernelILb1Ef"],
     "mlp_chain32.hip": ["gemm_chain_kernelILb0ELi2ELi2Ef"],
     "gemm_dw.hip": ["gemm_dw_kernelILb1Ef", "gemm_dw_kernelILb0Ef"],
-    "nmf_cf.hip": ["nmf_cf_bwd_tile_kernelILi1ELi1ELi4ELb0Ef", "nmf_cf_fwd_tile_kernelILi1ELi1ELi8ELb0Ef"],
+    "nmf_cf_bwd.hip": ["nmf_cf_bwd_tile_kernelILi1ELi1ELi4ELb0Ef"],
+    "nmf_cf_fwd.hip": ["nmf_cf_fwd_tile_kernelILi1ELi1ELi8ELb0Ef"],
     "nmf_cf_gram.hip": ["nmf_cf_bwd_gram_kernelILi4ELb0EfLi0E", "nmf_cf_bwd_gram_kernelILi4ELb0EDF16bLi2E"],
 }
 

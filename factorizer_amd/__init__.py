@@ -18,6 +18,8 @@ from .metrics import (DiceMetric, HausdorffDistanceMetric, dice_metric, discreti
                       segmentation_counts)
 from .augment import (AugmentParams, BatchAugment, affine_resample, augment_batch, draw_augment_params, gaussian_noise_field,
                       gaussian_smooth)
+from .volume import (BRATS_CLASSES, BRATS_LABEL_VALUES, PreparedVolume, foreground_bbox, normalize_intensity, prepare_volume,
+                     restore_prediction)
 from .training import FlatAdamW, WarmupCosineSchedule, load_checkpoint, load_checkpoints
 from .parallel import FlatGradSync
 from .inference import SlidingWindowInferer, SlidingWindowInfererAdapt, sliding_window_inference

@@ -215,6 +215,11 @@ class WgradDesc(_c.Structure):
                 ("act_dtype", _i), ("products", _i)]
 
 
+class VolGeom(_c.Structure):
+    """fz_vol_geom (include/factorizer_hip.h): axes lifted to three, z, y, x"""
+    _fields_ = [("nd", _i), ("size", _i * 3), ("start", _i * 3), ("end", _i * 3), ("pad", _i * 3), ("out", _i * 3)]
+
+
 _SIGS.update({
     "fz_gcorr_supported": ([_i] * 5, _i),
     "fz_gcorr": ([_vp] * 5 + [_i] * 11 + [_f, _vp], _i),
@@ -310,6 +315,15 @@ _SIGS.update({
     "fz_aug_resample": ([_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp], _i),
     "fz_aug_smooth": ([_vp, _vp, _i, _i, _vp, _vp] + [_i] * 6 + [_vp], _i),
     "fz_aug_noise_field": ([_vp, _vp, _i, _i, _i64, _vp], _i),
+    "fz_vol_kind_ok": ([_i, _i], _i),
+    "fz_vol_bbox": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
+    "fz_vol_workspace_bytes": ([_i, _c.POINTER(VolGeom)], _i64),
+    "fz_vol_stats": ([_vp, _i, _i, _c.POINTER(VolGeom), _i, _i, _vp, _vp], _i),
+    "fz_vol_write": ([_vp, _i, _vp, _i, _i, _vp, _i, _i, _c.POINTER(_i), _c.POINTER(_i), _i, _vp, _c.POINTER(VolGeom), _i, _i,
+                      _vp, _vp, _vp, _vp], _i),
+    "fz_vol_restore": ([_c.POINTER(_vp), _i, _i, _i, _c.POINTER(VolGeom), _f, _c.POINTER(_c.c_ubyte), _vp, _vp], _i),
 })
 SEG_F32, SEG_BF16, SEG_U8 = 0, 1, 2   # include/factorizer_hip.h: FZ_SEG_* element kinds of fz_seg_counts
+VOL_F32, VOL_BF16, VOL_U8, VOL_I16 = 0, 1, 2, 3   # include/factorizer_hip.h: FZ_VOL_* element kinds
+VOL_IMAGE_IN, VOL_IMAGE_OUT, VOL_LABEL_IN, VOL_LOGITS = 0, 1, 2, 3   # FZ_VOL_ROLE_*
 DROP_RES, DROP_GELU, DROP_GELU_BWD = 0, 1, 2   # include/factorizer_hip.h: FZ_DROP_*

@@ -6,6 +6,7 @@ route them to `composed.py`).  Backward passes are hand-written kernels as well
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 
@@ -793,3 +794,108 @@ def aug_apply(image, label, records, table_words, ns, seed):
                 *d3, N.stream_ptr(ref)), cols=ns * V)
             N.check(rc, "fz_aug_smooth")
     return out_i, out_l
+
+
+# ---- volume preparation and prediction restore (csrc/volprep.hip) -----------------------------------------------------
+_VOL_KIND = {torch.float32: N.VOL_F32, torch.bfloat16: N.VOL_BF16, torch.uint8: N.VOL_U8, torch.int16: N.VOL_I16}
+
+
+def vol_kind_ok(role, dtype) -> bool:
+    """fz_vol_kind_ok: does the role (N.VOL_IMAGE_IN, ...) take tensors of this dtype natively"""
+    return dtype in _VOL_KIND and bool(N.lib().fz_vol_kind_ok(role, _VOL_KIND[dtype]))
+
+
+def vol_geom(size, start, end, pad, out):
+    """fz_vol_geom of 1 to 3 spatial axes, lifted to three with leading unit axes"""
+    nd = len(size)
+    g = N.VolGeom()
+    g.nd = nd
+    lift = 3 - nd
+    for name, vals, fill in (("size", size, 1), ("start", start, 0), ("end", end, 1), ("pad", pad, 0), ("out", out, 1)):
+        arr = getattr(g, name)
+        for a in range(3):
+            arr[a] = fill if a < lift else int(vals[a - lift])
+    return g
+
+
+def vol_bbox(image):
+    """fz_vol_bbox over image (C, *S), fp32 or int16, contiguous: int32 device tensor {min z, y, x, max z, y, x} of the lifted
+    axes over the voxels where any channel is > 0 (min > max: none)"""
+    C = image.shape[0]
+    sp = tuple(image.shape[1:])
+    nd = len(sp)
+    d3 = (1,) * (3 - nd) + sp
+    box = torch.empty(6, dtype=torch.int32, device=image.device)
+    with _dev_guard(image):
+        rc = _timed("vol_bbox", image.numel() * image.element_size(), lambda: N.lib().fz_vol_bbox(
+            image.data_ptr(), _VOL_KIND[image.dtype], C, nd, *d3, box.data_ptr(), N.stream_ptr(image)), cols=math.prod(sp))
+    N.check(rc, "fz_vol_bbox")
+    return box
+
+
+def vol_prepare(image, label, geom, nonzero, channel_wise, classes, out_dtype):
+    """fz_vol_stats + fz_vol_write: image (C, *S) fp32 / int16 and the optional label — a class map (*S) uint8 / int16 with
+    `classes` (a sequence of id sequences), or (L, *S) uint8 with classes None — through `geom` (vol_geom).  Returns
+    (image (C, *out) of out_dtype, label (K, *out) uint8 or None, mean (C,), std (C,))."""
+    lib = N.lib()
+    C = image.shape[0]
+    nd = geom.nd
+    out_sp = tuple(geom.out[3 - nd:3])
+    box_sp = tuple(geom.end[a] - geom.start[a] for a in range(3 - nd, 3))
+    dev = image.device
+    nws = int(lib.fz_vol_workspace_bytes(C, ctypes.byref(geom)))
+    if nws < 0:
+        # let the entry point say what is wrong with the geometry
+        N.check(lib.fz_vol_stats(image.data_ptr(), _VOL_KIND[image.dtype], C, ctypes.byref(geom), int(nonzero),
+                                 int(channel_wise), None, N.stream_ptr(image)), "fz_vol_stats")
+        raise N.NativeError("fz_vol_workspace_bytes refused the geometry")
+    ws = torch.empty(nws // 8, dtype=torch.float64, device=dev)
+    out = torch.empty((C,) + out_sp, dtype=out_dtype, device=dev)
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    std = torch.empty(C, dtype=torch.float32, device=dev)
+    ids = counts = None
+    lab_out, lch, ncls, lkind = None, 0, 0, 0
+    if label is not None:
+        lkind = _VOL_KIND[label.dtype]
+        if classes is not None:
+            flat = [int(v) for cs in classes for v in cs]
+            ids = (ctypes.c_int * max(1, len(flat)))(*flat)
+            counts = (ctypes.c_int * len(classes))(*[len(cs) for cs in classes])
+            ncls = len(classes)
+        else:
+            lch = label.shape[0]
+        lab_out = torch.empty((ncls or lch,) + out_sp, dtype=torch.uint8, device=dev)
+    es = image.element_size()
+    nbox = C * math.prod(box_sp)
+    with _dev_guard(image):
+        rc = _timed("vol_stats", 2 * nbox * es, lambda: lib.fz_vol_stats(
+            image.data_ptr(), _VOL_KIND[image.dtype], C, ctypes.byref(geom), int(nonzero), int(channel_wise), ws.data_ptr(),
+            N.stream_ptr(image)), cols=math.prod(box_sp))
+        N.check(rc, "fz_vol_stats")
+        nbytes = nbox * es + out.numel() * out.element_size() + \
+            (0 if label is None else (lch or 1) * math.prod(box_sp) * label.element_size() + lab_out.numel())
+        rc = _timed("vol_write", nbytes, lambda: lib.fz_vol_write(
+            image.data_ptr(), _VOL_KIND[image.dtype], out.data_ptr(), _VOL_KIND[out_dtype], C, N.ptr(label), lkind, lch, ids,
+            counts, ncls, N.ptr(lab_out), ctypes.byref(geom), int(nonzero), int(channel_wise), ws.data_ptr(), mean.data_ptr(),
+            std.data_ptr(), N.stream_ptr(image)), cols=math.prod(out_sp))
+        N.check(rc, "fz_vol_write")
+    return out, lab_out, mean, std
+
+
+def vol_restore(logits, geom, bound, label_values):
+    """fz_vol_restore: logits = 1 to 8 contiguous (C, *out) tensors of one native kind; uint8 mask (C, *size), or with
+    label_values (C byte values) the label map (*size)"""
+    x = logits[0]
+    C, K = x.shape[0], len(logits)
+    nd = geom.nd
+    size = tuple(geom.size[3 - nd:3])
+    table = (ctypes.c_void_p * K)(*[t.data_ptr() for t in logits])
+    vals = None if label_values is None else (ctypes.c_ubyte * C)(*[int(v) for v in label_values])
+    res = torch.empty(size if label_values is not None else (C,) + size, dtype=torch.uint8, device=x.device)
+    box = math.prod(geom.end[a] - geom.start[a] for a in range(3))
+    with _dev_guard(x):
+        rc = _timed("vol_restore", K * C * box * x.element_size() + res.numel(), lambda: N.lib().fz_vol_restore(
+            table, K, _VOL_KIND[x.dtype], C, ctypes.byref(geom), float(bound), vals, res.data_ptr(), N.stream_ptr(x)),
+            cols=math.prod(size))
+    N.check(rc, "fz_vol_restore")
+    return res

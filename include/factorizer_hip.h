@@ -747,6 +747,61 @@ int fz_aug_smooth(const float* smooth_ws, void* img_out, int act_dtype, int C, c
                   int B, int nd, int D, int H, int W, fz_stream_t stream);
 int fz_aug_noise_field(float* out, const int64_t* seed, int B, int C, int64_t V, fz_stream_t stream);
 
+/* ---- volume preparation and prediction restore of the recipe, on device (csrc/volprep.hip; semantics:
+ * factorizer_amd/volume.py) ----
+ * `deterministic_transforms` of the bundles (model_zoo/factorizer_brats23/configs/train.yaml:86-116, inference.yaml:57-83):
+ * CropForegroundd(margin) -> NormalizeIntensityd(nonzero, channel_wise) -> BraTSOneHotEncoderd -> SpatialPadd(roi); and the
+ * inference `postprocessing` (inference.yaml:104-125): MeanEnsembled -> Activationsd(sigmoid) -> Invertd -> AsDiscreted ->
+ * label map.  An image is (C, D, H, W) dense with nd = 1, 2 or 3 spatial axes, a 2-D image passed as (1, H, W), a 1-D one as
+ * (1, 1, L).  Element kinds FZ_VOL_*; fz_vol_kind_ok(role, kind) says which kinds a role reads or writes: image in fp32 /
+ * int16, image out fp32 / bf16 (round to nearest even), label in uint8 / int16, logits fp32 / bf16.
+ * fz_vol_geom (axes lifted to three, z, y, x): `size` the image extent; [start, end) the crop box in image coordinates, which
+ *   may reach outside the image (those voxels read as 0); `pad` the zero voxels in front of the box in the prepared volume;
+ *   `out` its extent, out >= pad + end - start.  A lifted axis has size 1, start 0, end 1, pad 0, out 1.  The box must contain
+ *   at least one voxel of the image and every plane fewer than 2^31 voxels.  Anything else: FZ_E_ARG.
+ * fz_vol_bbox: box (6 int32, device) = {min z, y, x, max z, y, x} over the voxels where any channel is > 0; min > max when
+ *   there is none.  Integer atomics only: independent of the order.
+ * fz_vol_stats: per channel (channel_wise) or over all channels, the elements of the box that are selected — != 0 with
+ *   nonzero, else every one, the out-of-image zeros included — as float64 partials per workgroup in `workspace`
+ *   (fz_vol_workspace_bytes(C, geom) bytes): (count, sum), then the sum of squares about the float64 mean.  Two launches, no
+ *   float atomics; the partial count depends on the box shape alone and every reduction runs in a fixed order.
+ * fz_vol_write: out (C, out) of out_kind = 0 outside the box, x where x is not selected, else (x - mean) / std (IEEE
+ *   division) with mean, std = the float64 statistics rounded once to fp32; std = 1 when it rounds to 0 or nothing is
+ *   selected (then mean = 0).  mean, std (C) fp32 are written too.  The same launch encodes the label: label_channels = 0:
+ *   label is a class map (D, H, W) of label_kind and label_out (nclass, out) uint8 = 1 where the class id is in the set k
+ *   (class_ids holds the sets one after another, class_counts[k] ids each, 0 <= id < 32, nclass <= 8); label_channels = L > 0:
+ *   label is (L, D, H, W) uint8, cropped and padded as it is.  label = NULL: no label.
+ * fz_vol_restore: logits[k] (C, out) of `kind`, k < K <= 8; value = (sum in list order) * (1 / K) in fp32, foreground iff
+ *   value >= bound.  label_values = NULL: result (C, size) uint8 mask; else (C <= 8) result (size) uint8 = label_values[c] of
+ *   the first foreground channel, 0 when there is none.  Voxels outside the box are 0; every voxel of the result is written. */
+#define FZ_VOL_F32 0
+#define FZ_VOL_BF16 1
+#define FZ_VOL_U8 2
+#define FZ_VOL_I16 3
+#define FZ_VOL_ROLE_IMAGE_IN 0
+#define FZ_VOL_ROLE_IMAGE_OUT 1
+#define FZ_VOL_ROLE_LABEL_IN 2
+#define FZ_VOL_ROLE_LOGITS 3
+typedef struct fz_vol_geom {
+  int nd;
+  int size[3];
+  int start[3];
+  int end[3];
+  int pad[3];
+  int out[3];
+} fz_vol_geom;
+int fz_vol_kind_ok(int role, int kind);
+int fz_vol_bbox(const void* image, int kind, int C, int nd, int D, int H, int W, int32_t* box, fz_stream_t stream);
+int64_t fz_vol_workspace_bytes(int C, const fz_vol_geom* geom);
+int fz_vol_stats(const void* image, int kind, int C, const fz_vol_geom* geom, int nonzero, int channel_wise, void* workspace,
+                 fz_stream_t stream);
+int fz_vol_write(const void* image, int kind, void* out, int out_kind, int C, const void* label, int label_kind,
+                 int label_channels, const int* class_ids, const int* class_counts, int nclass, uint8_t* label_out,
+                 const fz_vol_geom* geom, int nonzero, int channel_wise, const void* workspace, float* mean, float* stdev,
+                 fz_stream_t stream);
+int fz_vol_restore(const void* const* logits, int K, int kind, int C, const fz_vol_geom* geom, float bound,
+                   const uint8_t* label_values, uint8_t* result, fz_stream_t stream);
+
 /* ---- AdamW over one flat buffer (torch.optim.AdamW of the training recipe,
  * model_zoo/factorizer_brats23/configs/train.yaml:72-76).  step >= 1 is the 1-based update count;
  * grad_scale multiplies the gradient first (1/world after a summed all-reduce). */

@@ -20,6 +20,8 @@ from .augment import (AugmentParams, BatchAugment, affine_resample, augment_batc
                       gaussian_smooth)
 from .volume import (BRATS_CLASSES, BRATS_LABEL_VALUES, PreparedVolume, foreground_bbox, normalize_intensity, prepare_volume,
                      restore_prediction)
+from .respace import (ResampleGeometry, SpacedVolume, orientation_of, prepare_spaced_volume, resample_volume,
+                      restore_spaced_prediction, spacing_geometry)
 from .training import FlatAdamW, WarmupCosineSchedule, load_checkpoint, load_checkpoints
 from .parallel import FlatGradSync
 from .inference import SlidingWindowInferer, SlidingWindowInfererAdapt, sliding_window_inference

@@ -220,6 +220,13 @@ class VolGeom(_c.Structure):
     _fields_ = [("nd", _i), ("size", _i * 3), ("start", _i * 3), ("end", _i * 3), ("pad", _i * 3), ("out", _i * 3)]
 
 
+class RespaceGeom(_c.Structure):
+    """fz_respace_geom (include/factorizer_hip.h): axes lifted to three, z, y, x"""
+    _fields_ = [("nd", _i), ("src_size", _i * 3), ("src_axis", _i * 3), ("flip", _i * 3), ("res_size", _i * 3), ("pad", _i * 3),
+                ("out", _i * 3), ("orig_size", _i * 3), ("box_start", _i * 3), ("scale", _c.c_double * 3),
+                ("inv_scale", _c.c_double * 3)]
+
+
 _SIGS.update({
     "fz_gcorr_supported": ([_i] * 5, _i),
     "fz_gcorr": ([_vp] * 5 + [_i] * 11 + [_f, _vp], _i),
@@ -322,8 +329,11 @@ _SIGS.update({
     "fz_vol_write": ([_vp, _i, _vp, _i, _i, _vp, _i, _i, _c.POINTER(_i), _c.POINTER(_i), _i, _vp, _c.POINTER(VolGeom), _i, _i,
                       _vp, _vp, _vp, _vp], _i),
     "fz_vol_restore": ([_c.POINTER(_vp), _i, _i, _i, _c.POINTER(VolGeom), _f, _c.POINTER(_c.c_ubyte), _vp, _vp], _i),
+    "fz_vol_respace": ([_vp, _i, _vp, _i, _vp, _i, _vp, _c.POINTER(RespaceGeom), _i, _vp], _i),
+    "fz_vol_unspace": ([_c.POINTER(_vp), _i, _i, _i, _c.POINTER(RespaceGeom), _i, _i, _f, _vp, _vp], _i),
 })
 SEG_F32, SEG_BF16, SEG_U8 = 0, 1, 2   # include/factorizer_hip.h: FZ_SEG_* element kinds of fz_seg_counts
 VOL_F32, VOL_BF16, VOL_U8, VOL_I16 = 0, 1, 2, 3   # include/factorizer_hip.h: FZ_VOL_* element kinds
 VOL_IMAGE_IN, VOL_IMAGE_OUT, VOL_LABEL_IN, VOL_LOGITS = 0, 1, 2, 3   # FZ_VOL_ROLE_*
+RESPACE_BILINEAR, RESPACE_NEAREST = 0, 1   # FZ_RESPACE_*
 DROP_RES, DROP_GELU, DROP_GELU_BWD = 0, 1, 2   # include/factorizer_hip.h: FZ_DROP_*

@@ -899,3 +899,60 @@ def vol_restore(logits, geom, bound, label_values):
             cols=math.prod(size))
     N.check(rc, "fz_vol_restore")
     return res
+
+
+# ---- resampling to the recipe's voxel spacing and back (csrc/respace.hip) ---------------------------------------------
+def respace_geom(src_size, src_axis, flip, scale, inv_scale, res_size, pad, out, orig_size, box_start):
+    """fz_respace_geom of 1 to 3 spatial axes, lifted to three with leading unit axes (a lifted axis reads itself)"""
+    nd = len(src_size)
+    g = N.RespaceGeom()
+    g.nd = nd
+    lift = 3 - nd
+    for name, vals, fill in (("src_size", src_size, 1), ("flip", flip, 0), ("res_size", res_size, 1), ("pad", pad, 0),
+                             ("out", out, 1), ("orig_size", orig_size, 1), ("box_start", box_start, 0)):
+        arr = getattr(g, name)
+        for a in range(3):
+            arr[a] = fill if a < lift else int(vals[a - lift])
+    for a in range(3):
+        g.src_axis[a] = a if a < lift else int(src_axis[a - lift]) + lift
+        g.scale[a] = 1.0 if a < lift else float(scale[a - lift])
+        g.inv_scale[a] = 1.0 if a < lift else float(inv_scale[a - lift])
+    return g
+
+
+def vol_respace(image, label, geom, mode, out_dtype):
+    """fz_vol_respace: image (C, *src) fp32 and the optional label (L, *src) uint8, both contiguous, through `geom`
+    (respace_geom) -> (image (C, *out) of out_dtype, label (L, *out) uint8 or None)"""
+    C = image.shape[0]
+    nd = geom.nd
+    out_sp = tuple(geom.out[3 - nd:3])
+    out = torch.empty((C,) + out_sp, dtype=out_dtype, device=image.device)
+    L = 0 if label is None else label.shape[0]
+    lab_out = None if label is None else torch.empty((L,) + out_sp, dtype=torch.uint8, device=image.device)
+    src = math.prod(geom.src_size[a] for a in range(3))
+    nbytes = C * src * 4 + out.numel() * out.element_size() + L * (src + math.prod(out_sp))   # every element once
+    with _dev_guard(image):
+        rc = _timed("vol_respace", nbytes, lambda: N.lib().fz_vol_respace(
+            image.data_ptr(), C, out.data_ptr(), _VOL_KIND[out_dtype], N.ptr(label), L, N.ptr(lab_out), ctypes.byref(geom),
+            int(mode), N.stream_ptr(image)), cols=math.prod(out_sp))
+    N.check(rc, "fz_vol_respace")
+    return out, lab_out
+
+
+def vol_unspace(logits, geom, sigmoid, threshold):
+    """fz_vol_unspace: logits = 1 to 8 contiguous (C, *out) tensors of one native kind -> uint8 mask (C, *orig_size) of
+    `value >= threshold`, or with threshold None the fp32 values"""
+    x = logits[0]
+    C, K = x.shape[0], len(logits)
+    nd = geom.nd
+    size = tuple(geom.orig_size[3 - nd:3])
+    table = (ctypes.c_void_p * K)(*[t.data_ptr() for t in logits])
+    res = torch.empty((C,) + size, dtype=torch.float32 if threshold is None else torch.uint8, device=x.device)
+    spaced = math.prod(geom.res_size[a] for a in range(3))
+    with _dev_guard(x):
+        rc = _timed("vol_unspace", K * C * spaced * x.element_size() + res.numel() * res.element_size(),
+                    lambda: N.lib().fz_vol_unspace(table, K, _VOL_KIND[x.dtype], C, ctypes.byref(geom), int(bool(sigmoid)),
+                                                   int(threshold is not None), float(threshold or 0.0), res.data_ptr(),
+                                                   N.stream_ptr(x)), cols=math.prod(size))
+    N.check(rc, "fz_vol_unspace")
+    return res

@@ -12,8 +12,9 @@ What the recipe runs (model_zoo/factorizer_brats23/configs; factorizer_isles22 h
   (inference.yaml:107-109) → ``Activationsd(sigmoid=True)`` (110-112) → ``Invertd`` (113-119; undoes the crop) →
   ``AsDiscreted(threshold=0.5)`` (120-122) → the BraTS label-map lambda (inference.yaml:123-125).
 
-``Orientationd`` and ``Spacingd`` (train.yaml:97-99, 104-108) need the file's affine and stay with the loader; both bundles
-run them at 1 mm on 1 mm data, where they are the identity.
+``Orientationd`` and ``Spacingd`` (train.yaml:97-99, 104-108) need the file's affine and are not part of this module: the BraTS
+bundles run them at 1 mm on 1 mm RAS data, where they are the identity; the ISLES22 bundles resample to 2 mm from files of
+mixed spacing and axis order, which is `respace.py` (`prepare_spaced_volume`, `restore_spaced_prediction`).
 
 MONAI (pinned 1.4.0) is third-party and absent here, so its semantics are **restated**, not pinned against it:
 
@@ -281,7 +282,8 @@ def prepare_volume(image, label=None, *, margin=10, roi_size=None, nonzero: bool
     ``classes[k]``; with ``classes=None`` an already channel-first uint8 (K, *S), cropped and padded as it is.  Returns a
     `PreparedVolume`: ``image`` (1, C, *P) in ``out_dtype`` (fp32 by default; bf16 is rounded to nearest even from the fp32
     value), ``label`` (1, K, *P) uint8 or None, the geometry and the (C,) fp32 ``mean`` / ``std`` that were applied.
-    ``Orientationd`` / ``Spacingd`` need file metadata and stay with the loader (the identity at the bundles' 1 mm)."""
+    ``Orientationd`` / ``Spacingd`` need the file's affine: the identity at the BraTS bundles' 1 mm, `prepare_spaced_volume`
+    otherwise."""
     _check_image(image)
     size = tuple(image.shape[1:])
     nd = len(size)

@@ -55,7 +55,7 @@ int fz_version(void);
  * compares fz_abi_version() with the FZ_ABI_VERSION of the header it was written against BEFORE the first call and refuses
  * to run on a mismatch (factorizer_amd/_native.py does).  History: 3 = round 3; 4 = round 4 (`products` / `tune` descriptor
  * fields, `products` argument of fz_conv3_*); 5 = round 5 (the two-window entry points fz_nmf_cf_fwd2 / _bwd2 removed, this
- * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended). */
+ * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace) leave it at 7. */
 #define FZ_ABI_VERSION 7
 int fz_abi_version(void);
 /* Walking order of the fused-core launches (fz_nmf_cf_fwd / fz_nmf_cf_bwd) this THREAD issues from now on: 0 = ascending over
@@ -801,6 +801,53 @@ int fz_vol_write(const void* image, int kind, void* out, int out_kind, int C, co
                  fz_stream_t stream);
 int fz_vol_restore(const void* const* logits, int K, int kind, int C, const fz_vol_geom* geom, float bound,
                    const uint8_t* label_values, uint8_t* result, fz_stream_t stream);
+
+/* ---- resampling to the recipe's voxel spacing and back, on device (csrc/respace.hip; semantics:
+ * factorizer_amd/respace.py) ----
+ * Orientationd(axcodes) -> Spacingd(pixdim, [bilinear, nearest], align_corners=True, padding_mode="border") -> SpatialPadd of
+ * the ISLES22 bundles (model_zoo/factorizer_isles22/configs/train.yaml:97-116) and the Invertd(nearest_interp=false) ->
+ * AsDiscreted of their postprocessing (inference.yaml:103-121).  Reorientation and respacing of a grid compose to a monomial
+ * map: every axis of the result reads ONE axis of the source at a position that is linear in its own index.
+ * fz_respace_geom (axes lifted to three, z, y, x; the host forms every number in it in float64):
+ *   src_size   the grid that is resampled (the crop box of the file's grid), in its own axis order;
+ *   src_axis   resampled axis w reads source axis src_axis[w] (a permutation); flip[w] != 0: against its direction;
+ *   res_size   the resampled extent; index o of axis w reads the ORIENTED position p = scale[w] * o (scale = pixdim / zoom),
+ *              clamped to [0, n - 1] with n = src_size[src_axis[w]]; oriented index i is source index flip ? n - 1 - i : i;
+ *   inv_scale  the way back: oriented index i reads resampled position inv_scale[w] * i (zoom / pixdim), clamped to
+ *              [0, res_size[w] - 1];
+ *   pad, out   zero voxels in front of the resampled grid in the padded volume and its extent, out >= pad + res_size;
+ *   orig_size, box_start   the file's grid and where src_size starts in it (source axis order; the box may leave the grid).
+ *   A lifted axis has size 1 everywhere, reads itself, is not flipped, pad 0, scales 1.  Every plane holds fewer than 2^31
+ *   voxels.  Anything else: FZ_E_ARG.
+ * Sampling: bilinear takes i0 = floor(p), i1 = min(i0 + 1, n - 1), weight (float)(p - i0), and lerps as fma(f, v1 - v0, v0)
+ *   in fp32 along the contiguous axis of the written grid's source order first (resampled axis 2, then 1, then 0); nearest
+ *   takes rint(p) (half to even).  Positions are float64.  When every scale is exactly 1 the bilinear mode runs the nearest
+ *   kernel: a copy, bit-identical to indexing.
+ * fz_vol_respace: image (C, src_size) fp32 -> out (C, out) of out_kind (fp32 / bf16, round to nearest even) in `mode`; label
+ *   (L, src_size) uint8 -> label_out (L, out), always nearest; L = 0: no label.  Pad voxels are written as 0; one launch.
+ * fz_vol_unspace: logits[k] (C, out) of `kind` (fp32 / bf16), k < K <= 8.  Per corner value = (sum in list order) * (1 / K)
+ *   in fp32, through 1 / (1 + exp(-value)) when sigmoid != 0; the corners are interpolated bilinearly through the inverse map
+ *   onto orig_size.  discretize != 0: result (C, orig_size) uint8 = value >= threshold; else fp32 values.  Voxels outside the
+ *   box are 0; every voxel of the result is written; one launch. */
+#define FZ_RESPACE_BILINEAR 0
+#define FZ_RESPACE_NEAREST 1
+typedef struct fz_respace_geom {
+  int nd;
+  int src_size[3];
+  int src_axis[3];
+  int flip[3];
+  int res_size[3];
+  int pad[3];
+  int out[3];
+  int orig_size[3];
+  int box_start[3];
+  double scale[3];
+  double inv_scale[3];
+} fz_respace_geom;
+int fz_vol_respace(const float* image, int C, void* out, int out_kind, const uint8_t* label, int L, uint8_t* label_out,
+                   const fz_respace_geom* geom, int mode, fz_stream_t stream);
+int fz_vol_unspace(const void* const* logits, int K, int kind, int C, const fz_respace_geom* geom, int sigmoid, int discretize,
+                   float threshold, void* result, fz_stream_t stream);
 
 /* ---- AdamW over one flat buffer (torch.optim.AdamW of the training recipe,
  * model_zoo/factorizer_brats23/configs/train.yaml:72-76).  step >= 1 is the 1-based update count;

@@ -284,6 +284,9 @@ _SIGS.update({
     "fz_upcat_compose": ([_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
     "fz_upcat_wgrads": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp], _i),
     "fz_upcat": ([_vp, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_vp], _i),
+    "fz_upcat_bwd_supported": ([_i] * 6, _i),
+    "fz_upcat_bwd_workspace_bytes": ([_i] * 4, _i64),
+    "fz_upcat_bwd": ([_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp] + [_i] * 7 + [_vp], _i),
     "fz_wgrad": ([_c.POINTER(WgradDesc), _vp, _vp], _i),
     "fz_wgrad_group": ([_c.POINTER(_c.POINTER(WgradDesc)), _c.POINTER(_vp), _i, _vp], _i),
     "fz_wgrad_workspace_bytes": ([_c.POINTER(WgradDesc)], _i64),

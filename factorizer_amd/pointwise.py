@@ -1336,6 +1336,37 @@ class UpCatLinearFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    def _backward_three(ctx, g, skip, deep, w2, wc, gw_ad, gb_ad, gt):
+        """the three launches over g (every shape the one-pass kernel does not take): (g_skip, g_deep); fills gw_ad[:, :C1], gb_ad, gt"""
+        B, Cd, D, H, W = deep.shape
+        V = D * H * W
+        Vf = 8 * V
+        C1 = skip.shape[1]
+        M = w2.shape[0]
+        O = w2.shape[1] - C1
+        dev = g.device
+        # --- skip half: input gradient + W_a weight gradient (+ Σ_v g) ---
+        if M == 32 and C1 == 32 and _dw_fused_ok(M, Vf):
+            g_skip, _, _, _, _ = _gemm_dw(g, w2[:, :C1], skip, want_bias=True, name="dgrad_wgrad",
+                                          gw_out=gw_ad[:, :C1], gb_out=gb_ad)
+        else:
+            g_skip = torch.empty_like(skip)
+            _gemm([g], w2, g_skip, B=B, Cin=M, Vin=Vf, M=C1, K=M, Ncol=Vf, w_t=True, ldw=C1 + O, name="linear_dgrad")
+            gwa = torch.empty((M, C1), dtype=torch.float32, device=dev)
+            with _no_defer():   # (the copy below reads the result inside this backward)
+                _wgrad(g, [skip], gwa, B=B, M=M, Cin=C1, K=C1, Vq=Vf, Ncols=Vf, gbias=gb_ad, name="wgrad_linear")
+            gw_ad[:, :C1].copy_(gwa)
+        # --- deep half: input gradient and the (deep x g) correlation, both on g itself ---
+        g_deep = None
+        if ctx.needs_input_grad[1]:
+            g_deep = torch.empty_like(deep)
+            _gemm([g], wc, g_deep, B=B, Cin=M, Vin=Vf, M=Cd, K=8 * M, Ncol=V, loader=LOAD_S2D,
+                  Di=2 * D, Hi=2 * H, Wi=2 * W, Ho=H, Wo=W, name="tconv_k2s2_dgrad")
+        _wgrad(deep, [g], gt, B=B, M=Cd, Cin=M, K=8 * M, Vq=Vf, Ncols=V, loader=LOAD_S2D, D=2 * D, H=2 * H,
+               W=2 * W, Ho=H, Wo=W, name="wgrad_tconv_k2s2")
+        return g_skip, g_deep
+
+    @staticmethod
     @_bwd
     def backward(ctx, g, _gt=None, _gst=None):
         skip, deep, w_t, w2, b_t = ctx.saved_tensors
@@ -1351,31 +1382,29 @@ class UpCatLinearFn(torch.autograd.Function):
         dev = g.device
         gw_ad = _GB.out_like(w2)
         gb_ad = torch.empty(M, dtype=torch.float32, device=dev)
-        # --- skip half: input gradient + W_a weight gradient (+ Σ_v g) ---
-        if M == 32 and C1 == 32 and _dw_fused_ok(M, Vf):
-            g_skip, _, _, _, _ = _gemm_dw(g, w2[:, :C1], skip, want_bias=True, name="dgrad_wgrad",
-                                          gw_out=gw_ad[:, :C1], gb_out=gb_ad)
-        else:
-            g_skip = torch.empty_like(skip)
-            _gemm([g], w2, g_skip, B=B, Cin=M, Vin=Vf, M=C1, K=M, Ncol=Vf, w_t=True, ldw=C1 + O, name="linear_dgrad")
-            gwa = torch.empty((M, C1), dtype=torch.float32, device=dev)
-            with _no_defer():   # (the copy below reads the result inside this backward)
-                _wgrad(g, [skip], gwa, B=B, M=M, Cin=C1, K=C1, Vq=Vf, Ncols=Vf, gbias=gb_ad, name="wgrad_linear")
-            gw_ad[:, :C1].copy_(gwa)
         w_b = w2[:, C1:]                                       # (M, O), row stride C1 + O
         wc = torch.empty((Cd, M, 2, 2, 2), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             N.check(N.lib().fz_upcat_compose(w_t.data_ptr(), w_b.data_ptr(), C1 + O, None, None, wc.data_ptr(), None, None,
                                              Cd, O, M, N.stream_ptr(g)), "fz_upcat_compose")
-        # --- deep half: input gradient and the (deep x g) correlation, both on g itself ---
-        g_deep = None
-        if ctx.needs_input_grad[1]:
-            g_deep = torch.empty_like(deep)
-            _gemm([g], wc, g_deep, B=B, Cin=M, Vin=Vf, M=Cd, K=8 * M, Ncol=V, loader=LOAD_S2D,
-                  Di=2 * D, Hi=2 * H, Wi=2 * W, Ho=H, Wo=W, name="tconv_k2s2_dgrad")
         gt = torch.empty((Cd, M, 8), dtype=torch.float32, device=dev)
-        _wgrad(deep, [g], gt, B=B, M=Cd, Cin=M, K=8 * M, Vq=Vf, Ncols=V, loader=LOAD_S2D, D=2 * D, H=2 * H,
-               W=2 * W, Ho=H, Wo=W, name="wgrad_tconv_k2s2")
+        if (M == 32 and ctx.needs_input_grad[1] and _UPCAT_BWD and skip.dtype == g.dtype == deep.dtype
+                and N.lib().fz_upcat_bwd_supported(C1, Cd, D, H, W, N.act_dtype(g))
+                and not ((g.data_ptr() | skip.data_ptr()) & 7 or deep.data_ptr() & 15)):
+            # one pass over (g, skip, deep) -> g_skip, g_deep and the partial rows of dW_a, Σ_v g, Gt (csrc/upcat_bwd.hip)
+            g_skip, g_deep = torch.empty_like(skip), torch.empty_like(deep)
+            ws = torch.empty(N.lib().fz_upcat_bwd_workspace_bytes(B, D, H, W) // 4, dtype=torch.float32, device=dev)
+            es = g.element_size()
+            with torch.cuda.device(dev), _finish_scope(ws, gt, gw_ad, gb_ad):
+                rc = Fn._timed(f"upcat_bwd_{Cd}->{M}", es * (3 * g.numel() + 2 * deep.numel()),
+                               lambda: N.lib().fz_upcat_bwd(g.data_ptr(), skip.data_ptr(), deep.data_ptr(), w2.data_ptr(), C1 + O,
+                                                            wc.data_ptr(), g_skip.data_ptr(), g_deep.data_ptr(), ws.data_ptr(),
+                                                            gw_ad.data_ptr(), C1 + O, gb_ad.data_ptr(), gt.data_ptr(), B, C1, Cd,
+                                                            D, H, W, N.act_dtype(g), N.stream_ptr(g)),
+                               cols=B * Vf, flops=4 * B * Vf * M * (C1 + Cd))
+            N.check(rc, "fz_upcat_bwd")
+        else:
+            g_skip, g_deep = UpCatLinearFn._backward_three(ctx, g, skip, deep, w2, wc, gw_ad, gb_ad, gt)
         gw_t = _GB.out_like(w_t)       # (its slice of the flat gradient buffer when one is attached)
         gb_t = torch.empty(O, dtype=torch.float32, device=dev) if ctx.has_bt else None
         with torch.cuda.device(dev), _finish_scope(gt, gb_ad, gw_t, gw_ad, gb_t):   # up = T(deep) + b_t: the constant part of up meets Σ_v g in dW_b
@@ -1386,6 +1415,7 @@ class UpCatLinearFn(torch.autograd.Function):
 
 
 _UPCAT_FWD = os.environ.get("FZ_UPCAT_FWD", "1") != "0"   # diagnostics: 0 = the two forward launches
+_UPCAT_BWD = os.environ.get("FZ_UPCAT_BWD", "1") != "0"   # diagnostics: 0 = the three backward launches over g
 _HEAD_BWD = os.environ.get("FZ_HEAD_BWD", "1") != "0"     # diagnostics: 0 = separate input- and weight-gradient launches
 
 

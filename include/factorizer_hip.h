@@ -486,6 +486,21 @@ int fz_upcat_wgrads(const float* gt, const float* w_t, const float* w_b, int ldb
 int fz_upcat_supported(int C, int Cd, int D, int H, int W);
 int fz_upcat(const void* skip, const void* deep, const float* wa, int lda, const float* wbt, const float* bias, void* out,
              int B, int C, int Cd, int D, int H, int W, int act_dtype, fz_stream_t stream);
+/* ---- decoder level backward in one pass over g = dL/d(out) ---------------------------------
+ * For the node above with 32 adapter outputs, C1 = 32 skip channels, Cd = 64 deep channels, fine W % 64 == 0 and fp32 storage
+ * (fz_upcat_bwd_supported; act_dtype FZ_STORE_BF16 answers 0: that storage keeps the three launches), ONE launch reads g, skip
+ * and deep once and forms
+ *   g_skip[c][v] = sum_m wa[m][c] g[m][v],   g_deep[k][n] = sum_{m,t} wc[k][m][t] g[m][fine(n,t)]   (wc from fz_upcat_compose)
+ * and, through per-workgroup partial rows in `workspace` (fz_upcat_bwd_workspace_bytes) that finish jobs add in index order
+ * (deferrable, see fz_finish_defer),
+ *   gw_a[m][c] = sum_v g[m][v] skip[c][v] (row stride ldg),  gb[m] = sum_v g[m][v],  gt[k][m][t] = sum_n deep[k][n] g[m][fine(n,t)]
+ * — the inputs of fz_upcat_wgrads.  g, skip, g_skip 8-byte aligned; deep, g_deep, workspace 16-byte aligned.
+ * (D, H, W) = coarse extent.  Outside the predicate: FZ_E_UNSUPPORTED; null pointer: FZ_E_ARG; B < 1: FZ_E_SHAPE. */
+int fz_upcat_bwd_supported(int C1, int Cd, int D, int H, int W, int act_dtype);
+int64_t fz_upcat_bwd_workspace_bytes(int B, int D, int H, int W);
+int fz_upcat_bwd(const void* g, const void* skip, const void* deep, const float* wa, int lda, const float* wc, void* g_skip,
+                 void* g_deep, void* workspace, float* gw_a, int ldg, float* gb, float* gt, int B, int C1, int Cd, int D, int H,
+                 int W, int act_dtype, fz_stream_t stream);
 /* [r5] The first layer of the FactorizerBlock that CONSUMES a 32-channel tensor, t = relu(in_proj(LayerNorm1(x)))
  * (factorizer.py:38,44,75; norm.py:29-34; in_proj has no bias), applied by the launch that PRODUCES x while the tile is in
  * registers: the launch that would read x back disappears (x itself is still written: the block's backward and its residual

@@ -16,8 +16,8 @@ from .blocks import FactMixer, FactorizerBlock, FactorizerStage
 from .losses import DiceCELoss, dice_bce_loss, dice_ce_loss
 from .metrics import (DiceMetric, HausdorffDistanceMetric, dice_metric, discretize, hausdorff_distance, mask_edges,
                       segmentation_counts)
-from .augment import (AugmentParams, BatchAugment, affine_resample, augment_batch, draw_augment_params, gaussian_noise_field,
-                      gaussian_smooth)
+from .augment import (AugmentParams, BatchAugment, RandCropAugment, affine_resample, augment_batch, crop_augment_batch,
+                      draw_augment_params, draw_crop_origins, gaussian_noise_field, gaussian_smooth)
 from .volume import (BRATS_CLASSES, BRATS_LABEL_VALUES, PreparedVolume, foreground_bbox, normalize_intensity, prepare_volume,
                      restore_prediction)
 from .respace import (ResampleGeometry, SpacedVolume, orientation_of, prepare_spaced_volume, resample_volume,

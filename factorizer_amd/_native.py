@@ -325,6 +325,8 @@ _SIGS.update({
     "fz_aug_resample": ([_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp], _i),
     "fz_aug_smooth": ([_vp, _vp, _i, _i, _vp, _vp] + [_i] * 6 + [_vp], _i),
     "fz_aug_noise_field": ([_vp, _vp, _i, _i, _i64, _vp], _i),
+    "fz_aug_source_words": ([], _i),
+    "fz_aug_crop_resample": ([_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp], _i),
     "fz_vol_kind_ok": ([_i, _i], _i),
     "fz_vol_bbox": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "fz_vol_workspace_bytes": ([_i, _c.POINTER(VolGeom)], _i64),

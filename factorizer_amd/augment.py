@@ -44,6 +44,24 @@ it) and one smoothing launch over the samples that drew one (none: no launch).  
 implement the same contract, Philox restated with integer tensor ops; device tensors outside the gate (fp16 / fp64, 1-D,
 σ ≥ 1.125, i.e. more than 9 taps) run those composed ops on device and say so once.  Nothing here needs autograd; the outputs
 do not require grad.
+
+**Random crop.**  The first entry of the recipe's ``random_transforms`` is ``RandSpatialCropd(roi_size, random_size=False)``
+with its default ``random_center=True``; restated (MONAI's numpy stream is not reproduced, for the reason given above): per
+sample and spatial axis ``k`` an integer origin ``g_k`` uniform in ``[0, N_k − roi_k]`` (`draw_crop_origins`); the sample is
+the box ``[g, g + roi)`` of its source, and every step above then runs on that box — step 1 with ``N = roi``, border padding
+at the crop's border.  `crop_augment_batch` takes the B sources where they are (ragged shapes, e.g. the
+``PreparedVolume.image`` tensors kept in HBM as the bundles' ``CacheDataset(cache_rate=1.0)`` keeps them on the host), and
+
+    crop_augment_batch([x_i], [l_i], g, roi, params) == augment_batch(stack(x_i[box_i]), stack(l_i[box_i]), params)
+
+bit for bit on every path: the positions of step 1 are formed in crop coordinates and clamped to ``[0, roi_k − 1]`` by the
+same arithmetic, the integer origin is added to the integer corner indices afterwards, no voxel outside a box is read, and
+the noise counter stays the flat OUTPUT voxel.  Natively (csrc/aug_crop.hip) the crop costs the gather a base pointer, two
+strides and three offsets per sample, which travel with the records in the one host-to-device copy of the batch: one launch,
+plus the smoothing launch if a sample drew one.  The gate is `augment_batch`'s on the roi and the dtypes, plus: every source
+contiguous (made so otherwise, with a one-time warning: a full copy of that source per call), every source plane below 2³¹
+voxels, B and the plane counts within the grid limits.  Outside it the boxes are sliced and stacked and `augment_batch`'s
+paths take over.  `RandCropAugment` is the module: crop origins first, then the records, from one generator.
 """
 from __future__ import annotations
 
@@ -400,8 +418,23 @@ def _records(params: AugmentParams, nd: int):
     return buf, len(listed)
 
 
-def _is_label(t) -> bool:
-    return t.dtype in (torch.uint8, torch.bool)
+def _outside_gate(B, planes, spatial, image_dtype, label_dtype, params):
+    """why a batch of B samples x `planes` planes of the spatial shape `spatial` (the OUTPUT geometry) is outside the native
+    kernel set, or None; a dtype of None: no such tensor"""
+    nd = len(spatial)
+    if nd not in (2, 3):
+        return f"{nd} spatial axis"
+    if image_dtype is not None and image_dtype not in (torch.float32, torch.bfloat16):
+        return f"{image_dtype} image"
+    if label_dtype is not None and label_dtype not in (torch.uint8, torch.bool):
+        return f"{label_dtype} label"
+    if max(spatial) > MAX_AXIS or math.prod(spatial) >= 2 ** 31:
+        return f"spatial shape {tuple(spatial)}"
+    if B > 65535 or planes > 65535:
+        return "more than 65535 samples or planes"
+    if params is not None and not native_sigma_ok(params.sigma):
+        return "a sigma of 1.125 or more (over 9 taps)"
+    return None
 
 
 def _gate(image, label, params, what):
@@ -409,20 +442,9 @@ def _gate(image, label, params, what):
     ref = image if image is not None else label
     if not ref.is_cuda or ref.numel() == 0:
         return False
-    nd = ref.dim() - 2
-    why = None
-    if nd not in (2, 3):
-        why = f"{nd} spatial axis"
-    elif image is not None and image.dtype not in (torch.float32, torch.bfloat16):
-        why = f"{image.dtype} image"
-    elif label is not None and not _is_label(label):
-        why = f"{label.dtype} label"
-    elif max(ref.shape[2:]) > MAX_AXIS or math.prod(ref.shape[2:]) >= 2 ** 31:
-        why = f"spatial shape {tuple(ref.shape[2:])}"
-    elif ref.shape[0] > 65535 or (0 if image is None else image.shape[1]) + (0 if label is None else label.shape[1]) > 65535:
-        why = "more than 65535 samples or planes"
-    elif params is not None and not native_sigma_ok(params.sigma):
-        why = "a sigma of 1.125 or more (over 9 taps)"
+    why = _outside_gate(ref.shape[0], (0 if image is None else image.shape[1]) + (0 if label is None else label.shape[1]),
+                        tuple(ref.shape[2:]), None if image is None else image.dtype, None if label is None else label.dtype,
+                        params)
     if why is None:
         return True
     composed.warn_once(f"augment:{what}:{why}", f"{what}: {why} is outside the native kernel set (fp32 / bf16 image, uint8 / "
@@ -442,9 +464,12 @@ def _check(image, label, params):
         raise TypeError(f"the image must be a floating-point tensor, got {image.dtype}")
     if image is not None and label is not None and image.device != label.device:
         raise ValueError("image and label live on different devices")
-    nd = ref.dim() - 2
-    if params.batch != ref.shape[0] or params.spatial_dims != nd:
-        raise ValueError(f"records for B = {params.batch}, nd = {params.spatial_dims}; tensors have B = {ref.shape[0]}, nd = {nd}")
+    _check_records(params, ref.shape[0], ref.dim() - 2)
+
+
+def _check_records(params, B, nd):
+    if params.batch != B or params.spatial_dims != nd:
+        raise ValueError(f"records for B = {params.batch}, nd = {params.spatial_dims}; tensors have B = {B}, nd = {nd}")
     for name, shape in (("flip", (params.batch, nd)), ("noise_std", (params.batch,)), ("sigma", (params.batch, nd)),
                         ("gain", (params.batch,)), ("offset", (params.batch,))):
         if tuple(getattr(params, name).shape) != shape:
@@ -456,7 +481,12 @@ def augment_batch(image, label, params: AugmentParams):
     docstring defines; returns ``(image, label)`` as new tensors of the same dtypes.  Deterministic: the same tensors, records
     and seed give bitwise the same result."""
     _check(image, label, params)
-    if not _gate(image, label, params, "augment_batch"):
+    return _run(image, label, params, _gate(image, label, params, "augment_batch"))
+
+
+def _run(image, label, params, native):
+    """the checked call on the path its gate chose"""
+    if not native:
         with torch.no_grad():
             return _augment_composed(image, label, params)
     ref = image if image is not None else label
@@ -492,13 +522,182 @@ def gaussian_smooth(image, sigma):
     return augment_batch(image, None, p)[0]
 
 
+# ---- random crop inside the gather -----------------------------------------------------------------------------------------
+SRC = 8    # include/factorizer_hip.h: fz_aug_source_words()
+
+
+def _roi(roi_size, nd):
+    roi = (int(roi_size),) * nd if isinstance(roi_size, int) else tuple(int(r) for r in roi_size)
+    if len(roi) != nd or min(roi) < 1:
+        raise ValueError(f"roi_size needs one positive extent per spatial axis ({nd}), got {roi_size}")
+    return roi
+
+
+def draw_crop_origins(shapes, roi_size, generator=None) -> torch.Tensor:
+    """The origins of ``RandSpatialCropd(roi_size, random_size=False)`` for a batch: int64 CPU tensor ``(B, nd)``, origin ``k``
+    of sample ``b`` uniform over the integers ``[0, N_k − roi_k]``.  ``shapes``: B spatial shapes; a tensor ``(C, *S)`` or
+    ``(1, C, *S)`` stands for its ``S`` (the last ``len(roi_size)`` axes; an int ``roi_size`` needs shapes, not tensors).  All
+    origins come from ONE ``torch.rand`` call in float64 on the CPU ``generator`` (None: torch's default), ``g = floor(u · (N −
+    roi + 1))``, so a generator state determines them; ``roi_k == N_k`` gives 0, ``roi_k > N_k`` raises."""
+    shapes = list(shapes)
+    if not shapes:
+        raise ValueError("no shapes given")
+    if isinstance(roi_size, int):
+        if any(torch.is_tensor(sh) for sh in shapes):
+            raise ValueError("an int roi_size needs spatial shapes (a tensor's spatial axes are counted by len(roi_size))")
+        nd = len(shapes[0])
+    else:
+        nd = len(tuple(roi_size))
+    roi = _roi(roi_size, nd)
+    sp = []
+    for b, sh in enumerate(shapes):
+        t = tuple(int(n) for n in (sh.shape[-nd:] if torch.is_tensor(sh) else sh))
+        if len(t) != nd:
+            raise ValueError(f"sample {b}: spatial shape {t} does not have {nd} axes")
+        for k in range(nd):
+            if roi[k] > t[k]:
+                raise ValueError(f"sample {b}, axis {k}: roi {roi[k]} exceeds the extent {t[k]} (pad the volume to the roi first)")
+        sp.append(t)
+    free = torch.tensor(sp, dtype=torch.float64) - torch.tensor(roi, dtype=torch.float64)     # N - roi, (B, nd)
+    u = torch.rand(len(sp), nd, generator=generator, dtype=torch.float64)
+    return torch.minimum(torch.floor(u * (free + 1)), free).to(torch.int64)
+
+
+def _crop_sources(images, labels, origins, roi_size):
+    """checked views of one batch: (images, labels) as lists of (C, *S_i) / (L, *S_i) tensors or None, origins as a list of
+    B tuples, roi"""
+    origins = torch.as_tensor(origins).detach().to("cpu", torch.int64)
+    if origins.dim() != 2:
+        raise ValueError("origins must be (B, nd)")
+    B, nd = origins.shape
+    if nd < 1 or nd > 3:
+        raise ValueError("1 to 3 spatial axes")
+    roi = _roi(roi_size, nd)
+    if images is None and labels is None:
+        raise ValueError("neither images nor labels given")
+    out = []
+    for name, seq in (("image", images), ("label", labels)):
+        if seq is None:
+            out.append(None)
+            continue
+        seq = list(seq)
+        if len(seq) != B:
+            raise ValueError(f"{len(seq)} {name}s for {B} origins")
+        ts = []
+        for b, t in enumerate(seq):
+            if t.dim() == nd + 2 and t.shape[0] == 1:
+                t = t[0]                                                  # PreparedVolume.image is (1, C, *P)
+            if t.dim() != nd + 1:
+                raise ValueError(f"{name} {b}: expected (C, *S) or (1, C, *S) with {nd} spatial axes, got {tuple(t.shape)}")
+            if ts and t.shape[0] != ts[0].shape[0]:
+                raise ValueError(f"{name} {b} has {t.shape[0]} channels, {name} 0 has {ts[0].shape[0]}")
+            if ts and (t.dtype != ts[0].dtype or t.device != ts[0].device):
+                raise ValueError(f"{name} {b} is {t.dtype} on {t.device}, {name} 0 is {ts[0].dtype} on {ts[0].device}")
+            ts.append(t)
+        out.append(ts)
+    imgs, labs = out
+    if imgs is not None and not imgs[0].is_floating_point():
+        raise TypeError(f"the images must be floating-point tensors, got {imgs[0].dtype}")
+    if imgs is not None and labs is not None:
+        if imgs[0].device != labs[0].device:
+            raise ValueError("images and labels live on different devices")
+        for b in range(B):
+            if imgs[b].shape[1:] != labs[b].shape[1:]:
+                raise ValueError(f"sample {b}: image {tuple(imgs[b].shape)} and label {tuple(labs[b].shape)} differ in "
+                                 "spatial shape")
+    g = [tuple(row) for row in origins.tolist()]
+    for b, t in enumerate(imgs if imgs is not None else labs):
+        for k in range(nd):
+            if g[b][k] < 0 or g[b][k] + roi[k] > t.shape[1 + k]:
+                raise ValueError(f"sample {b}, axis {k}: box [{g[b][k]}, {g[b][k] + roi[k]}) leaves the extent {t.shape[1 + k]}")
+    return imgs, labs, g, roi
+
+
+def _crop_table(imgs, labs, g, roi):
+    """the source table of one batch: int64 CPU tensor (B, SRC) = image address, label address (0: none), the three source
+    extents, the three origins — 2-D lifted with a leading extent 1 / origin 0 (layout: include/factorizer_hip.h)"""
+    ref = imgs if imgs is not None else labs
+    pad = 3 - len(roi)
+    rows = [[imgs[b].data_ptr() if imgs is not None else 0, labs[b].data_ptr() if labs is not None else 0,
+             *((1,) * pad + tuple(ref[b].shape[1:])), *((0,) * pad + tuple(g[b]))] for b in range(len(ref))]
+    return torch.tensor(rows, dtype=torch.int64)
+
+
+def source_vector_loads(table, roi, image_bytes=4):
+    """Which samples of a source table (`_crop_table`) the kernel reads with vector loads on the identity path, restating
+    csrc/aug_crop.hip: bool (B, 2) for (image, label).  The output side must allow vectors at all (roi W a multiple of 4);
+    then every lane's first element must sit on a 4-byte boundary: always for fp32, origin x and source W even and the base
+    4-byte aligned for bf16, all three multiples of 4 for the one-byte label."""
+    t = torch.as_tensor(table, dtype=torch.int64)
+    per = 4 // int(image_bytes)                                           # elements per 4 bytes
+    out = torch.full((t.shape[0],), int(roi[-1]) % 4 == 0)
+    img = out & (t[:, 0] != 0) & (t[:, 7] % per == 0) & (t[:, 4] % per == 0) & (t[:, 0] % 4 == 0)
+    lab = out & (t[:, 1] != 0) & (t[:, 7] % 4 == 0) & (t[:, 4] % 4 == 0) & (t[:, 1] % 4 == 0)
+    return torch.stack([img, lab], dim=1)
+
+
+def _box(t, g, roi):
+    return t[(slice(None),) + tuple(slice(o, o + r) for o, r in zip(g, roi))]
+
+
+def crop_augment_batch(images, labels, origins, roi_size, params: AugmentParams = None):
+    """Cut the box ``[origins[b], origins[b] + roi_size)`` out of every sample's own source and apply the records ``params``
+    to the batch of boxes, as the module docstring defines: returns ``(image (B, C, *roi), label (B, L, *roi))``, bit for bit
+    what `augment_batch` gives on the stacked boxes.  ``images`` / ``labels``: sequences of B tensors ``(C, *S_b)`` or
+    ``(1, C, *S_b)`` (either may be None; a tensor may appear more than once); ``origins``: integers ``(B, nd)``, e.g. from
+    `draw_crop_origins`; ``params=None``: identity records, i.e. a pure batched crop.  Sources and the call share the current
+    stream."""
+    imgs, labs, g, roi = _crop_sources(images, labels, origins, roi_size)
+    ref = imgs if imgs is not None else labs
+    B, nd = len(ref), len(roi)
+    if params is None:
+        params = AugmentParams.identity(B, nd)
+    C = imgs[0].shape[0] if imgs is not None else 0
+    L = labs[0].shape[0] if labs is not None else 0
+    idt = imgs[0].dtype if imgs is not None else None
+    ldt = labs[0].dtype if labs is not None else None
+    native = ref[0].is_cuda and (C + L) * math.prod(roi) > 0
+    if native:
+        why = _outside_gate(B, C + L, roi, idt, ldt, params)
+        if why is None and any(math.prod(t.shape[1:]) >= 2 ** 31 for t in ref):
+            why = "a source plane of 2^31 voxels or more"
+            composed.warn_once(f"augment:crop_augment_batch:{why}", f"crop_augment_batch: {why} is outside the native crop "
+                               "kernel (32-bit in-plane offsets): the boxes are sliced and stacked first")
+        native = why is None
+    if not native:
+        image = torch.stack([_box(t, g[b], roi) for b, t in enumerate(imgs)]) if imgs is not None else None
+        label = torch.stack([_box(t, g[b], roi) for b, t in enumerate(labs)]) if labs is not None else None
+        _check(image, label, params)
+        return _run(image, label, params, _gate(image, label, params, "crop_augment_batch"))
+    _check_records(params, B, nd)
+    if not all(t.is_contiguous() for seq in (imgs, labs) if seq is not None for t in seq):
+        composed.warn_once("augment:crop_augment_batch:contiguous", "crop_augment_batch: a source is not contiguous and is "
+                           "copied whole on every call (one read and one write of the full volume); keep the prepared volumes "
+                           "contiguous")
+        imgs = [t.contiguous() for t in imgs] if imgs is not None else None
+        labs = [t.contiguous() for t in labs] if labs is not None else None
+    rec, ns = _records(params, nd)
+    table = _crop_table(imgs, labs, g, roi)
+    buf = torch.empty(2 * SRC * B + rec.numel(), dtype=torch.float32)
+    buf[:2 * SRC * B].view(torch.int64).copy_(table.reshape(-1))          # the table first: its words are 8-byte aligned
+    buf[2 * SRC * B:].view(torch.int32).copy_(rec.view(torch.int32))
+    dev = ref[0].device
+    dev_buf = buf.to(dev, non_blocking=True)                               # still the one host-to-device copy of the batch
+    seed = None
+    if imgs is not None and bool((params.noise_std > 0).any()):
+        seed = _seed_tensor(params.seed, dev)
+    with torch.no_grad():                                                  # imgs / labs stay referenced until the launches are enqueued
+        return Fn.aug_crop_apply(dev_buf, 2 * SRC * B, B * REC, ns, seed, roi, C, L, idt, ldt)
+
+
 class BatchAugment(torch.nn.Module):
     """The recipe's ``random_transforms`` for a whole batch: ``aug(image, label=None, generator=None)`` draws one record per
     sample (`draw_augment_params`; ``generator``: a CPU ``torch.Generator``) and applies it (`augment_batch`), returning
     ``(image, label)``.  The defaults are the recipe's.  In ``eval()`` mode it is the identity and returns the same objects.
 
         aug = ft.BatchAugment(3)
-        for image, label in loader:                       # the loaders only load, crop and stack
+        for image, label in loader:                       # the loaders only load, crop and stack (`RandCropAugment`
+                                                          # crops volumes that are already on the device)
             image, label = aug(image.cuda(non_blocking=True), label.cuda(non_blocking=True))
             loss = loss_fn(model(image), label)
     """
@@ -525,3 +724,39 @@ class BatchAugment(torch.nn.Module):
 
     def extra_repr(self):
         return f"spatial_dims={self.spatial_dims}, " + ", ".join(f"{k}={v}" for k, v in self.kwargs.items())
+
+
+class RandCropAugment(torch.nn.Module):
+    """The recipe's whole ``random_transforms`` list, the leading ``RandSpatialCropd(roi_size, random_size=False)`` included,
+    on sources that already sit on the device: ``aug(images, labels=None, generator=None)`` takes B tensors ``(C, *S_b)`` or
+    ``(1, C, *S_b)`` of any sizes ≥ roi, draws the crop origins (`draw_crop_origins`) and THEN one record per sample
+    (`draw_augment_params`) from the same CPU ``generator``, and applies both in one gather (`crop_augment_batch`), returning
+    ``(image (B, C, *roi), label (B, L, *roi))``.  The keyword arguments are `BatchAugment`'s.  In ``eval()`` mode it takes the
+    centred box ``g_k = (N_k − roi_k) // 2`` with identity records.
+
+        cache = [ft.prepare_volume(x, l, roi_size=roi) for x, l in subjects]         # prepared volumes stay in HBM
+        aug = ft.RandCropAugment(3, roi)
+        for idx in batches:
+            image, label = aug([cache[i].image for i in idx], [cache[i].label for i in idx])
+            loss = loss_fn(model(image), label)
+    """
+
+    def __init__(self, spatial_dims, roi_size, **kwargs):
+        super().__init__()
+        self.spatial_dims = int(spatial_dims)
+        self.roi_size = _roi(roi_size, self.spatial_dims)
+        self.kwargs = BatchAugment(self.spatial_dims, **kwargs).kwargs       # the same defaults, validated the same way
+
+    def forward(self, images, labels=None, generator=None):
+        ref = list(images if images is not None else labels)
+        if self.training:
+            origins = draw_crop_origins(ref, self.roi_size, generator)
+            params = draw_augment_params(len(ref), self.spatial_dims, generator=generator, **self.kwargs)
+        else:
+            shapes = torch.tensor([tuple(t.shape[-self.spatial_dims:]) for t in ref], dtype=torch.int64)
+            origins = torch.div(shapes - torch.tensor(self.roi_size), 2, rounding_mode="floor")
+            params = None
+        return crop_augment_batch(images, labels, origins, self.roi_size, params)
+
+    def extra_repr(self):
+        return f"spatial_dims={self.spatial_dims}, roi_size={self.roi_size}, " + ", ".join(f"{k}={v}" for k, v in self.kwargs.items())

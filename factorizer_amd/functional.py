@@ -796,6 +796,40 @@ def aug_apply(image, label, records, table_words, ns, seed):
     return out_i, out_l
 
 
+def aug_crop_apply(buf, source_words, table_words, ns, seed, roi, C, L, image_dtype, label_dtype):
+    """fz_aug_crop_resample over a batch whose samples are cut from their own source volumes (csrc/aug_crop.hip), then
+    fz_aug_smooth over its `ns` smoothing samples.  `buf`: the device copy of augment._crop_table — `source_words` fp32 words
+    that hold the int64 source table, then `table_words` words of records, then the int32 sample list.  roi: the output's
+    spatial shape; C / L planes of image_dtype / label_dtype per sample (0: none); seed as in aug_apply.  The caller keeps the
+    source tensors alive until this returns.  Returns new (image (B, C, *roi), label (B, L, *roi))."""
+    lib = N.lib()
+    roi = tuple(int(r) for r in roi)
+    nd = len(roi)
+    d3 = (1,) * (3 - nd) + roi
+    V = math.prod(roi)
+    B = table_words // int(lib.fz_aug_record_floats())
+    if int(lib.fz_aug_record_floats()) * B != table_words or 2 * int(lib.fz_aug_source_words()) * B != source_words:
+        raise N.NativeError("the record or source-table layout of augment.py and of the library differ")
+    out_i = torch.empty((B, C) + roi, dtype=image_dtype, device=buf.device) if C else None
+    out_l = torch.empty((B, L) + roi, dtype=label_dtype, device=buf.device) if L else None
+    ns = ns if C else 0
+    ws = torch.empty((ns, C, V), dtype=torch.float32, device=buf.device) if ns else None
+    dt = N.act_dtype(out_i) if C else N.STORE_F32
+    es = out_i.element_size() if C else 0
+    records = buf.data_ptr() + 4 * source_words
+    with _dev_guard(buf):
+        rc = _timed("aug_crop_resample", B * V * (2 * C * es + 2 * L), lambda: lib.fz_aug_crop_resample(
+            buf.data_ptr(), N.ptr(out_i), dt, C, N.ptr(out_l), L, records, N.ptr(seed), N.ptr(ws), ns, B, nd, *d3,
+            N.stream_ptr(buf)), cols=B * V)
+        N.check(rc, "fz_aug_crop_resample")
+        if ns:
+            rc = _timed("aug_smooth", ns * C * V * (4 + es), lambda: lib.fz_aug_smooth(
+                ws.data_ptr(), out_i.data_ptr(), dt, C, records, records + 4 * table_words, ns, B, nd, *d3,
+                N.stream_ptr(buf)), cols=ns * V)
+            N.check(rc, "fz_aug_smooth")
+    return out_i, out_l
+
+
 # ---- volume preparation and prediction restore (csrc/volprep.hip) -----------------------------------------------------
 _VOL_KIND = {torch.float32: N.VOL_F32, torch.bfloat16: N.VOL_BF16, torch.uint8: N.VOL_U8, torch.int16: N.VOL_I16}
 

@@ -55,7 +55,7 @@ int fz_version(void);
  * compares fz_abi_version() with the FZ_ABI_VERSION of the header it was written against BEFORE the first call and refuses
  * to run on a mismatch (factorizer_amd/_native.py does).  History: 3 = round 3; 4 = round 4 (`products` / `tune` descriptor
  * fields, `products` argument of fz_conv3_*); 5 = round 5 (the two-window entry points fz_nmf_cf_fwd2 / _bwd2 removed, this
- * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace) leave it at 7. */
+ * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words) leave it at 7. */
 #define FZ_ABI_VERSION 7
 int fz_abi_version(void);
 /* Walking order of the fused-core launches (fz_nmf_cf_fwd / fz_nmf_cf_bwd) this THREAD issues from now on: 0 = ascending over
@@ -753,7 +753,27 @@ int fz_edge_min_dist2(const float* q, int64_t nq, const float* t, int64_t nt, fl
  *   gain / offset, stored to img_out sample b in act_dtype (one rounding).  One launch: a workgroup holds an output tile and
  *   its 4-voxel halo in LDS for all passes.  ns = 0 launches nothing.
  * fz_aug_noise_field: out (B, C, V) fp32 = z(b, c, v) alone.
- * FZ_E_ARG: null pointer, aliasing input / output, bad act_dtype, nd outside {2, 3}; FZ_E_SHAPE: sizes, an extent above 2048. */
+ * fz_aug_crop_resample: fz_aug_resample with the random crop of the recipe (RandSpatialCropd(roi_size, random_size=False), the
+ *   first entry of `random_transforms`) cut inside the gather: D, H, W are the ROI = the output extents, and sample b is read
+ *   from its own source volume at its own integer origin.  `sources`: B entries of fz_aug_source_words() = 8 int64 words in
+ *   DEVICE memory, 8-byte aligned (factorizer_amd/augment.py puts them in front of the records, in the same host-to-device
+ *   copy):
+ *     [0] address of the sample's image (C, sD, sH, sW) of act_dtype, dense   (ignored when C = 0)
+ *     [1] address of the sample's label (L, sD, sH, sW) uint8 / bool, dense   (ignored when L = 0)
+ *     [2..4] source extents sD, sH, sW     [5..7] origin gz, gy, gx of the box [g, g + roi) inside the source
+ *   A 2-D source is passed as sD = 1, gz = 0.  Output voxel o of sample b reads box position p = A (o' - c) + c with
+ *   c_k = (roi_k - 1) / 2, clamped to [0, roi_k - 1]: the arithmetic of fz_aug_resample in crop coordinates (border padding
+ *   at the CROP's border); the integer corner indices derived from p are then offset by g.  No voxel outside the box is read,
+ *   and the result equals fz_aug_resample run on a dense copy of the boxes, bit for bit; noise counters (the flat OUTPUT
+ *   voxel), smoothing slots and gain / offset as there, fz_aug_smooth follows unchanged.  Source extents are not limited to
+ *   2048, only to fewer than 2^31 voxels per source plane (in-plane offsets are 32-bit; the 64-bit plane base is formed once
+ *   per workgroup).  The kernel SKIPS a sample — reads nothing through its entry, writes nothing for it — whose entry has a
+ *   null base where a plane is expected (or an image base not aligned to its element), a box that does not lie inside the
+ *   extents, or a source plane of 2^31 voxels or more.  On the identity path a sample whose gx, sW and base put every
+ *   lane's first element on a 4-byte boundary (fp32: always; bf16: gx and sW even, base 4-byte aligned; label: gx, sW and
+ *   base multiples of 4) is read with one vector load per lane, any other with four scalar loads: same bits.
+ * FZ_E_ARG: null pointer or table, aliasing input / output, bad act_dtype, nd outside {2, 3}; FZ_E_SHAPE: sizes, an (output)
+ * extent above 2048. */
 int fz_aug_record_floats(void);
 int fz_aug_resample(const void* img, void* img_out, int act_dtype, int C, const uint8_t* lab, uint8_t* lab_out, int L,
                     const float* table, const int64_t* seed, float* smooth_ws, int ns, int B, int nd, int D, int H, int W,
@@ -761,6 +781,9 @@ int fz_aug_resample(const void* img, void* img_out, int act_dtype, int C, const 
 int fz_aug_smooth(const float* smooth_ws, void* img_out, int act_dtype, int C, const float* table, const int32_t* list, int ns,
                   int B, int nd, int D, int H, int W, fz_stream_t stream);
 int fz_aug_noise_field(float* out, const int64_t* seed, int B, int C, int64_t V, fz_stream_t stream);
+int fz_aug_source_words(void);
+int fz_aug_crop_resample(const int64_t* sources, void* img_out, int act_dtype, int C, uint8_t* lab_out, int L, const float* table,
+                         const int64_t* seed, float* smooth_ws, int ns, int B, int nd, int D, int H, int W, fz_stream_t stream);
 
 /* ---- volume preparation and prediction restore of the recipe, on device (csrc/volprep.hip; semantics:
  * factorizer_amd/volume.py) ----

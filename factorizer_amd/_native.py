@@ -232,6 +232,9 @@ _SIGS.update({
     "fz_gcorr": ([_vp] * 5 + [_i] * 11 + [_f, _vp], _i),
     "fz_gcorr_wgrad_workspace_bytes": ([_i] * 10, _i64),
     "fz_gcorr_wgrad": ([_vp] * 4 + [_i] * 11 + [_vp], _i),
+    "fz_gcorr_act": ([_vp] * 5 + [_i] * 11 + [_f, _i, _vp], _i),
+    "fz_gcorr_wgrad_act": ([_vp] * 4 + [_i] * 12 + [_vp], _i),
+    "fz_gcorr_mu_bwd": ([_vp] * 8 + [_i] * 11 + [_f, _i, _vp], _i),
     "fz_gnmf_supported": ([_i, _i64, _i, _i, _i], _i),
     "fz_gnmf_workspace_bytes": ([_i64, _i, _i64, _i, _i, _i], _i64),
     "fz_gnmf_launches": ([_i, _i, _i], _i),

@@ -19,10 +19,20 @@ Evaluation here: every operator is a grouped ``F.conv{1,2,3}d``.  While the filt
 once they depend on the sample the batch is folded into the groups.  Hᵀx + ε does not depend on s, so it is
 computed once per call, not once per iteration.  The 1×1 projections, LayerNorm and MLP around the mixer run
 the native GEMM-family kernels on device (factorizer_amd/pointwise.py); H, Hᵀ and their input gradients run
-the native grouped-correlation kernel (csrc/deconv.hip: fp32, ≤ 16 channels per group, cubic or square 3/5/7
-kernels; iterations without gradient fuse the update and the division into its epilogue); the filter gradient and
+the native grouped-correlation kernels (csrc/deconv_kernels.h: any odd kernel extent ≤ 7 per axis, any channel count
+per group; iterations without gradient fuse the update and the division into the epilogue); the filter gradient and
 `update_filter`'s lag correlations — the same reduction over all voxels — run `fz_gcorr_wgrad` (deterministic
 two-stage sums).  Shapes outside that set use framework convolutions on device, announced once by a RuntimeWarning.
+
+Storage: the layer follows the type of its input, float32 or bfloat16 (the mixed-precision mode: `ft.Deconver` under
+``torch.autocast("cuda", dtype=torch.bfloat16)``, or a bfloat16 input).  On bfloat16 the sources s, Hᵀx + ε, H s and the
+returned sources are STORED as bf16; the kernels convert to fp32 on load, multiply, accumulate and divide in fp32 and round
+once per stored element.  The filters h and all that derives from them (their grouped / adjoint views, `normalize_h`, the
+`update_filter` ratio and its lag correlations) and every parameter gradient stay fp32.  An iteration that carries a
+gradient is one autograd node there (functional.GCorrMuFn: the backward recomputes the denominator in the kernel), so the
+update stores one tensor, not three; on float32 such an iteration keeps the composed expression s ∘ num / (Hᵀ(H s) + ε).
+The composed fallback (CPU tensors, even kernel extents) computes bf16 inputs in fp32 and rounds where the device stores.
+float16 is not supported: ε = 1e-16 underflows in it.
 """
 from __future__ import annotations
 
@@ -62,6 +72,24 @@ def _gcorr(inp: Tensor, w: Tensor, padding) -> Tensor:
     return out.reshape(B, G * Cout, *out.shape[2:])
 
 
+def _no_autocast(t: Tensor):
+    """the composed bf16 path states its own precision: fp32 arithmetic, explicit roundings"""
+    return torch.autocast(device_type=t.device.type, enabled=False)
+
+
+def _gcorr_as_stored(inp: Tensor, w: Tensor, padding, add_eps: float = 0.0, rounded: bool = True) -> Tensor:
+    """`_gcorr` (+ eps) for either storage type: a bfloat16 input is computed in fp32 against the fp32 filters and — if
+    `rounded` — rounded once, as the native kernel stores it; float32 takes the plain expression."""
+    if inp.dtype != torch.bfloat16:
+        out = _gcorr(inp, w, padding)
+        return out + add_eps if add_eps else out
+    with _no_autocast(inp):
+        out = _gcorr(inp.float(), w.float(), padding)
+        if add_eps:
+            out = out + add_eps
+        return out.to(inp.dtype) if rounded else out
+
+
 def _lag_corr(s: Tensor, x: Tensor, G: int, padding) -> Tensor:
     """corr(s, x)[b, g, c, k, τ] = Σ_v s[b, g·K + k, v + τ − p] · x[b, g·C + c, v]  for the lags τ of the kernel
     support (deconvolution.py:43-50 `sconv` + the transpose of `update_h`) → (B, G, C, K, *kernel)."""
@@ -91,7 +119,11 @@ class DeconvInitializer(nn.Module):
         self.linear = Linear(channels, groups * source_channels)
 
     def forward(self, x: Tensor):
-        s = F.relu(self.linear(x))
+        if x.dtype == torch.bfloat16 and not x.is_cuda:   # composed: fp32 arithmetic, rounded where the device stores
+            with _no_autocast(x):
+                s = F.relu(self.linear(x.float()).to(x.dtype))
+        else:
+            s = F.relu(self.linear(x))
         h = F.relu(self.h0).expand(x.shape[0], *self.h0.shape)
         return s, h
 
@@ -139,17 +171,17 @@ class Deconv(nn.Module):
         return (h + self.eps) / (h.sum([d for d in range(h.ndim) if d not in (0, 2)], keepdim=True) + self.eps)
 
     # ---- operators ------------------------------------------------------------------------------------
-    def _corr(self, inp: Tensor, wg: Tensor, add_eps: float = 0.0) -> Tensor:
-        """grouped correlation (+ eps): the native gfx950 kernel (csrc/deconv.hip) on device where it applies"""
+    def _corr(self, inp: Tensor, wg: Tensor, add_eps: float = 0.0, rounded: bool = True) -> Tensor:
+        """grouped correlation (+ eps): the native gfx950 kernel (csrc/deconv.hip) on device where it applies
+        (`rounded=False`: the composed bfloat16 path hands back its fp32 value, for a consumer that rounds later)"""
         if Fn.gcorr_supported(inp, wg):
             return Fn.gcorr(inp, wg, add_eps)
         if inp.is_cuda and inp.numel():
             composed.warn_once(f"deconv{tuple(inp.shape[1:])}{tuple(wg.shape)}",
                                f"Deconv: grouped correlation {tuple(wg.shape)} on {tuple(inp.shape)} ({inp.dtype}) is outside "
-                               "the native kernel set (fp32, odd kernel extents <= 7); "
+                               "the native kernel set (float32 or bfloat16, odd kernel extents <= 7); "
                                "using framework convolutions on device")
-        out = _gcorr(inp, wg, self.padding)
-        return out + add_eps if add_eps else out
+        return _gcorr_as_stored(inp, wg, self.padding, add_eps, rounded)
 
     def _lags(self, s: Tensor, x: Tensor) -> Tensor:
         """corr(s, x) over the lags of the kernel support → (B, G, C/G, K, *kernel): fz_gcorr_wgrad on device"""
@@ -157,8 +189,11 @@ class Deconv(nn.Module):
             return Fn.lag_corr(s, x, self.groups, self.kernel_size)
         if x.is_cuda and x.numel():
             composed.warn_once("deconv_update_h", "Deconv(update_filter=True): lag correlations outside the native kernel "
-                               "set (fp32, odd kernel extents <= 7); using framework "
+                               "set (float32 or bfloat16, odd kernel extents <= 7); using framework "
                                "convolutions on device")
+        if s.dtype == torch.bfloat16 or x.dtype == torch.bfloat16:   # the lag correlations are fp32 on either storage
+            with _no_autocast(s):
+                return _lag_corr(s.float(), x.float(), self.groups, self.padding)
         return _lag_corr(s, x, self.groups, self.padding)
 
     def _H(self, s: Tensor, hg: Tensor) -> Tensor:
@@ -166,6 +201,20 @@ class Deconv(nn.Module):
 
     def _Ht(self, r: Tensor, hg: Tensor, add_eps: float = 0.0) -> Tensor:
         return self._corr(r, _adjoint_filters(hg), add_eps)
+
+    def _update_s(self, s: Tensor, num: Tensor, r: Tensor, hT: Tensor) -> Tensor:
+        """s ∘ num / (corr(r, hT) + ε)"""
+        graded = torch.is_grad_enabled() and (s.requires_grad or num.requires_grad or r.requires_grad or hT.requires_grad)
+        native = Fn.gcorr_supported(r, hT) and s.dtype == r.dtype and num.dtype == r.dtype
+        if native and not graded:
+            return Fn.gcorr_mu_update(s, num, r, hT, self.eps)          # update + division fused in the kernel
+        if s.dtype != torch.bfloat16:
+            return s * num / self._corr(r, hT, self.eps)
+        if native:
+            return Fn.gcorr_mu_update_graded(s, num, r, hT, self.eps)   # one node, one stored tensor
+        den = self._corr(r, hT, self.eps, rounded=False)   # composed: the quotient is what the device stores, not den
+        with _no_autocast(s):
+            return (s.float() * num.float() / den.float()).to(s.dtype)
 
     def context(self, it: int):
         return torch.no_grad() if it < self.num_iters - self.num_grad_iters + 1 else nullcontext()
@@ -186,13 +235,7 @@ class Deconv(nn.Module):
                     else:
                         num = shared_num[key]
                     r = self._H(s, hg)
-                    hT = _adjoint_filters(hg)
-                    no_grad_needed = not (torch.is_grad_enabled() and (s.requires_grad or num.requires_grad
-                                                                       or r.requires_grad or hT.requires_grad))
-                    if no_grad_needed and Fn.gcorr_supported(r, hT):
-                        s = Fn.gcorr_mu_update(s, num, r, hT, self.eps)      # update + division fused in the kernel
-                    else:
-                        s = s * num / self._corr(r, hT, self.eps)
+                    s = self._update_s(s, num, r, _adjoint_filters(hg))
                 if self.update_filter:
                     num_h = self._lags(s, x) + self.eps
                     den_h = self._lags(s, self._H(s, hg)) + self.eps
@@ -219,7 +262,7 @@ class Deconv(nn.Module):
         """relative error per sample of the (already group-split, as in the reference) operands"""
         Bg = x.shape[0]
         hg = h.reshape(Bg, 1, *h.shape[1:])
-        return relative_error(x, _gcorr(s, hg, self.padding))
+        return relative_error(x, _gcorr_as_stored(s, hg, self.padding))
 
     def forward(self, x: Tensor) -> Tensor:
         s, h = self._start(x)

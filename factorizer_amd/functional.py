@@ -530,8 +530,13 @@ def _k3(w):
     return (1,) * (3 - len(k)) + k
 
 
+def _act_ok(*ts) -> bool:
+    """activation operands of the grouped-correlation kernels: all fp32 or all bf16 (csrc/deconv_kernels.h, storage type AT)"""
+    return ts[0].dtype in (torch.float32, torch.bfloat16) and all(t.dtype == ts[0].dtype for t in ts)
+
+
 def gcorr_supported(inp, w) -> bool:
-    if not (inp.is_cuda and inp.numel() and inp.dtype == torch.float32 and w.dtype == torch.float32):
+    if not (inp.is_cuda and inp.numel() and _act_ok(inp) and w.dtype == torch.float32):
         return False
     if inp.dim() not in (4, 5) or w.dim() != inp.dim() + 2 or w.shape[0] not in (1, inp.shape[0]):
         return False
@@ -543,18 +548,22 @@ def gcorr_supported(inp, w) -> bool:
 
 
 def _gcorr_raw(inp, w, add_eps=0.0, mul_a=None, mul_b=None):
+    """out = corr(inp, w) + add_eps, or mul_a ∘ mul_b / (corr + add_eps): activations fp32 or bf16 (one type), w fp32"""
     B = inp.shape[0]
     Bw, G, Co, Ci = w.shape[:4]
     sp = tuple(inp.shape[2:])
     D, H, W = (1,) * (3 - len(sp)) + sp
+    if w.dtype != torch.float32 or not _act_ok(inp, *(t for t in (mul_a, mul_b) if t is not None)):
+        raise TypeError("grouped correlation: activations of one type (float32 or bfloat16), float32 filters")
     out = torch.empty((B, G * Co, *sp), dtype=inp.dtype, device=inp.device)
     kd, kh, kw = _k3(w)
     with _dev_guard(inp):
-        rc = _timed(f"gcorr_{Ci}->{Co}_k{kd}{kh}{kw}", 4 * (inp.numel() + out.numel() * (3 if mul_a is not None else 1)),
-                    lambda: N.lib().fz_gcorr(inp.data_ptr(), w.data_ptr(), out.data_ptr(), N.ptr(mul_a), N.ptr(mul_b), B, G,
-                                             Ci, Co, D, H, W, kd, kh, kw, int(Bw != 1), float(add_eps),
-                                             N.stream_ptr(inp)))
-    N.check(rc, "fz_gcorr")
+        rc = _timed(f"gcorr_{Ci}->{Co}_k{kd}{kh}{kw}",
+                    inp.element_size() * (inp.numel() + out.numel() * (3 if mul_a is not None else 1)),
+                    lambda: N.lib().fz_gcorr_act(inp.data_ptr(), w.data_ptr(), out.data_ptr(), N.ptr(mul_a), N.ptr(mul_b), B, G,
+                                                 Ci, Co, D, H, W, kd, kh, kw, int(Bw != 1), float(add_eps),
+                                                 N.act_dtype(inp), N.stream_ptr(inp)))
+    N.check(rc, "fz_gcorr_act")
     return out
 
 
@@ -564,27 +573,52 @@ def adjoint_filters(w):
 
 
 def _gcorr_wgrad_raw(inp, gout, w_shape):
-    """gw (Bw, G, Co, Ci, *k) of out = corr(inp, w): fz_gcorr_wgrad (deterministic two-stage reduction)"""
+    """gw (Bw, G, Co, Ci, *k), fp32, of out = corr(inp, w): fz_gcorr_wgrad_act (deterministic two-stage reduction)"""
     B = inp.shape[0]
     Bw, G, Co, Ci = w_shape[:4]
     sp = tuple(inp.shape[2:])
     D, H, W = (1,) * (3 - len(sp)) + sp
     ks = tuple(w_shape[4:])
     kd, kh, kw = (1,) * (3 - len(ks)) + ks
+    if not _act_ok(inp, gout):
+        raise TypeError("grouped correlation filter gradient: input and output gradient of one type (float32 or bfloat16)")
     gw = torch.empty(tuple(w_shape), dtype=torch.float32, device=inp.device)
     nb = N.lib().fz_gcorr_wgrad_workspace_bytes(B, G, Ci, Co, D, H, W, kd, kh, kw)
     ws = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=inp.device)
     with _dev_guard(inp):
-        rc = _timed(f"gcorr_wgrad_{Ci}->{Co}_k{kd}{kh}{kw}", 4 * (inp.numel() + gout.numel()),
-                    lambda: N.lib().fz_gcorr_wgrad(inp.data_ptr(), gout.data_ptr(), gw.data_ptr(), ws.data_ptr(), B, G, Ci, Co,
-                                                   D, H, W, kd, kh, kw, int(Bw != 1), N.stream_ptr(inp)))
-    N.check(rc, "fz_gcorr_wgrad")
+        rc = _timed(f"gcorr_wgrad_{Ci}->{Co}_k{kd}{kh}{kw}", inp.element_size() * (inp.numel() + gout.numel()),
+                    lambda: N.lib().fz_gcorr_wgrad_act(inp.data_ptr(), gout.data_ptr(), gw.data_ptr(), ws.data_ptr(), B, G, Ci,
+                                                       Co, D, H, W, kd, kh, kw, int(Bw != 1), N.act_dtype(inp),
+                                                       N.stream_ptr(inp)))
+    N.check(rc, "fz_gcorr_wgrad_act")
     return gw
+
+
+def _gcorr_mu_bwd_raw(r, wT, g, s, num, eps, want):
+    """(ds, dnum, dden) of s' = s ∘ num / (corr(r, wT) + eps) from g = dL/ds' in one launch (fz_gcorr_mu_bwd: the denominator
+    is recomputed, not read); `want` = (ds?, dnum?, dden?) — an output that is not wanted is None and not written"""
+    flags = [bool(f) for f in want]
+    B = r.shape[0]
+    Bw, G, Co, Ci = wT.shape[:4]
+    sp = tuple(r.shape[2:])
+    D, H, W = (1,) * (3 - len(sp)) + sp
+    if wT.dtype != torch.float32 or not _act_ok(r, g, s, num):
+        raise TypeError("multiplicative-update backward: activations of one type (float32 or bfloat16), float32 filters")
+    outs = [torch.empty_like(s) if f else None for f in flags]
+    kd, kh, kw = _k3(wT)
+    with _dev_guard(r):
+        rc = _timed(f"gcorr_mu_bwd_{Ci}->{Co}_k{kd}{kh}{kw}", r.element_size() * (r.numel() + s.numel() * (3 + sum(flags))),
+                    lambda: N.lib().fz_gcorr_mu_bwd(r.data_ptr(), wT.data_ptr(), g.data_ptr(), s.data_ptr(), num.data_ptr(),
+                                                    N.ptr(outs[0]), N.ptr(outs[1]), N.ptr(outs[2]), B, G, Ci, Co, D, H, W,
+                                                    kd, kh, kw, int(Bw != 1), float(eps), N.act_dtype(r), N.stream_ptr(r)))
+    N.check(rc, "fz_gcorr_mu_bwd")
+    return outs
 
 
 class GCorrFn(torch.autograd.Function):
     """out = corr(inp, w) + add_eps: native forward, input gradient (the adjoint correlation) and filter gradient
-    (the lag-correlation of inp with the output gradient, fz_gcorr_wgrad)."""
+    (the lag-correlation of inp with the output gradient, fz_gcorr_wgrad).  Activations and their gradients in the
+    storage type of `inp` (fp32 or bf16), the filter gradient in fp32."""
 
     @staticmethod
     def forward(ctx, inp, w, add_eps):
@@ -604,10 +638,35 @@ class GCorrFn(torch.autograd.Function):
         return ginp, gw, None
 
 
+class GCorrMuFn(torch.autograd.Function):
+    """s' = s ∘ num / (corr(r, wT) + eps) as ONE node: the forward is the fused-epilogue launch, the backward recomputes the
+    denominator in the kernel (fz_gcorr_mu_bwd) — saved are s, num, r and wT, which exist anyway; den, s ∘ num and the
+    quotient are never stored.  From dden the gradients of r (the adjoint correlation) and of wT (the filter gradient) follow.
+    On bf16 storage every tensor that reaches memory is rounded once."""
+
+    @staticmethod
+    def forward(ctx, s, num, r, wT, eps):
+        s, num, r, wT = s.contiguous(), num.contiguous(), r.contiguous(), wT.contiguous()
+        ctx.save_for_backward(s, num, r, wT)
+        ctx.eps = float(eps)
+        return _gcorr_raw(r, wT, eps, s, num)
+
+    @staticmethod
+    def backward(ctx, g):
+        s, num, r, wT = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        ds, dnum, dden = _gcorr_mu_bwd_raw(r, wT, g.contiguous(), s, num, ctx.eps,
+                                           (need[0], need[1], need[2] or need[3]))
+        dr = _gcorr_raw(dden, adjoint_filters(wT)) if need[2] else None
+        dwT = _gcorr_wgrad_raw(r, dden, wT.shape) if need[3] else None
+        return ds, dnum, dr, dwT, None
+
+
 class LagCorrFn(torch.autograd.Function):
     """L[b, g, c, k, τ] = Σ_v x[b, g·C + c, v] · s[b, g·K + k, v + τ − p] — the lag correlations of the filter update
     (deconvolution.py:43-50 `sconv`, :150-156 `update_h`).  The same reduction as the filter gradient of the grouped
-    correlation (fz_gcorr_wgrad); its own gradients are two grouped correlations with gL as per-sample filters."""
+    correlation (fz_gcorr_wgrad); its own gradients are two grouped correlations with gL as per-sample filters.
+    s and x in one storage type (fp32 or bf16); L and gL are fp32."""
 
     @staticmethod
     def forward(ctx, s, x, G, ksize):
@@ -619,7 +678,7 @@ class LagCorrFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gL):
         s, x = ctx.saved_tensors
-        gL = gL.contiguous()
+        gL = gL.float().contiguous()
         gs = gx = None
         if ctx.needs_input_grad[0]:
             gs = _gcorr_raw(x, adjoint_filters(gL))
@@ -629,7 +688,7 @@ class LagCorrFn(torch.autograd.Function):
 
 
 def lag_corr_supported(s, x, G, ksize) -> bool:
-    if not (s.is_cuda and s.numel() and s.dtype == torch.float32 and x.dtype == torch.float32 and s.dim() in (4, 5)):
+    if not (s.is_cuda and s.numel() and _act_ok(s, x) and s.dim() in (4, 5)):
         return False
     K, C = s.shape[1] // G, x.shape[1] // G
     k3 = (1,) * (3 - len(ksize)) + tuple(int(k) for k in ksize)
@@ -648,6 +707,12 @@ def gcorr_mu_update(s, num, r, wT, eps):
     """s ∘ num / (corr(r, wT) + eps) in one launch — for iterations that carry no gradient (inference, or the
     leading `num_iters − num_grad_iters` iterations of deconvolution.py:158-166)."""
     return _gcorr_raw(r.contiguous(), wT.contiguous(), eps, s.contiguous(), num.contiguous())
+
+
+def gcorr_mu_update_graded(s, num, r, wT, eps):
+    """the same update as an autograd node (GCorrMuFn): gradients with respect to s, num, r and wT, two stored tensors
+    (the result and, in the backward, dden) where the composed expression stores five"""
+    return GCorrMuFn.apply(s, num, r, wT, eps)
 
 
 # ---- block dropout masks (csrc/dropout.hip) ---------------------------------------------------------------------------

@@ -55,7 +55,7 @@ int fz_version(void);
  * compares fz_abi_version() with the FZ_ABI_VERSION of the header it was written against BEFORE the first call and refuses
  * to run on a mismatch (factorizer_amd/_native.py does).  History: 3 = round 3; 4 = round 4 (`products` / `tune` descriptor
  * fields, `products` argument of fz_conv3_*); 5 = round 5 (the two-window entry points fz_nmf_cf_fwd2 / _bwd2 removed, this
- * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words) leave it at 7. */
+ * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words; fz_gcorr_act / fz_gcorr_wgrad_act / fz_gcorr_mu_bwd: the grouped correlations on bf16 storage) leave it at 7. */
 #define FZ_ABI_VERSION 7
 int fz_abi_version(void);
 /* Walking order of the fused-core launches (fz_nmf_cf_fwd / fz_nmf_cf_bwd) this THREAD issues from now on: 0 = ascending over
@@ -635,6 +635,26 @@ int fz_gcorr(const float* in, const float* w, float* out, const float* mul_a, co
 int64_t fz_gcorr_wgrad_workspace_bytes(int B, int G, int Ci, int Co, int D, int H, int W, int kd, int kh, int kw);
 int fz_gcorr_wgrad(const float* in, const float* gout, float* gw, void* ws, int B, int G, int Ci, int Co, int D, int H,
                    int W, int kd, int kh, int kw, int w_batched, fz_stream_t stream);
+/* The same operators on either activation storage type (act_dtype FZ_STORE_F32 / FZ_STORE_BF16; anything else is
+ * FZ_E_UNSUPPORTED): in, out, mul_a, mul_b and gout are activations (float* or bf16 by act_dtype, all of one type); the
+ * filters w, the filter gradient gw and the workspace are always fp32.  bf16 values are converted to fp32 as the tile is
+ * staged, every product and accumulator is fp32 (the fused update is computed in fp32 as well), and each stored element is
+ * rounded to nearest-even once.  fz_gcorr / fz_gcorr_wgrad are these with FZ_STORE_F32.  The filter gradient adds in a fixed
+ * order for both types: repeated calls agree bit for bit. */
+int fz_gcorr_act(const void* in, const float* w, void* out, const void* mul_a, const void* mul_b, int B, int G,
+                 int Ci, int Co, int D, int H, int W, int kd, int kh, int kw, int w_batched, float add_eps,
+                 int act_dtype, fz_stream_t stream);
+int fz_gcorr_wgrad_act(const void* in, const void* gout, float* gw, void* ws, int B, int G, int Ci, int Co, int D, int H,
+                       int W, int kd, int kh, int kw, int w_batched, int act_dtype, fz_stream_t stream);
+/* Backward of the fused multiplicative update s' = s * num / den, den = corr(r, wT) + eps, in ONE launch: den is recomputed in
+ * the accumulators (it is never stored), and from g = dL/ds'
+ *   ds = g * num / den,   dnum = g * s / den,   dden = -g * s * num / den^2
+ * are written.  r (B, G*Ci, D, H, W); g, s, num, ds, dnum, dden (B, G*Co, D, H, W), activations of act_dtype; wT as w above.
+ * Each of ds / dnum / dden may be NULL and is then not written (at least one must be given).  The gradients of r and wT follow
+ * from dden: fz_gcorr_act(dden, adjoint filters) and fz_gcorr_wgrad_act(r, dden). */
+int fz_gcorr_mu_bwd(const void* r, const float* wT, const void* g, const void* s, const void* num, void* ds, void* dnum,
+                    void* dden, int B, int G, int Ci, int Co, int D, int H, int W, int kd, int kh, int kw, int w_batched,
+                    float eps, int act_dtype, fz_stream_t stream);
 
 /* ---- fused soft-Dice + BCE-with-logits loss (training step; the form of the bundle's
  * DiceCELoss(sigmoid=True, squared_pred=True), model_zoo/factorizer_brats23/configs/train.yaml:67-70).

@@ -7,11 +7,12 @@ Each autograd Function below is one fused layer of the reference block:
   ActLinearResFn  res + Linear([GELU](z)) + bias           mlp.py:54-60 / factorizer.py:53,75-76
   LinearFn        plain Linear                              linear.py:53-58
   CatLinearFn     Linear(cat([x1, x2], 1)) without the cat  unet.py:128 + factorizer.py:116
-  ConvK2S2Fn / TConvK2S2Fn / ConvK3Fn / ConvK1            unet.py:53,123,231,253
-  ConvK2S2Fn2d / SkipConvK2S2Fn2d / TConvK2S2Fn2d / ConvK3Fn2d   the same layers of a 2-D U-shape
+  ConvK2S2Fn / SkipConvK2S2Fn / TConvK2S2Fn / ConvK3Fn / ConvK1   unet.py:53,123,231,253 — 4-D or 5-D activations: the
+                                                            same nodes serve a 2-D and a 3-D U-shape (_RANK)
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import threading as _threading
@@ -27,7 +28,7 @@ from . import functional as Fn
 ACT = {"none": 0, "relu": 1, "gelu": 2}
 LOAD_PLAIN, LOAD_S2D, LOAD_K3, LOAD_S2D_2D, LOAD_K3_2D = 0, 1, 2, 3, 4
 EPI_PLAIN, EPI_D2S, EPI_D2S_2D = 0, 1, 3
-QL_S2D_2D, QL_K3_2D = 3, 4
+QL_S2D_2D, QL_K3_2D = LOAD_S2D_2D, LOAD_K3_2D   # fz_wgrad's own names of the two ids (FZ_QL_* in the header): nothing here passes them
 _D2S_FINE = {EPI_D2S: 8, EPI_D2S_2D: 4}   # fine voxels per coarse column of a depth-to-space epilogue
 
 
@@ -853,20 +854,40 @@ class LayerNormFn(torch.autograd.Function):
         return gx, ggamma, gbeta, None
 
 
-# ---- strided convolutions of the U-shape ------------------------------------------------------------
+# ---- strided convolutions of the U-shape, 2-D (Conv2d / ConvTranspose2d) and 3-D ---------------------------------------
+# Tap orders (weights are used in place, no packing pass): k2s2 rows / columns k = (c, th, tw) = c*4 + th*2 + tw, i.e. the
+# row-major flattening of Conv2d's (O, C, 2, 2) weight and ConvTranspose2d's (C, O, 2, 2) weight; k3p1 k = (c, kh, kw) =
+# c*9 + kh*3 + kw, the flattening of (O, C, 3, 3).  DESIGN.md §3 "2-D tap geometries".  3-D: the same with a leading depth tap,
+# k = (c, td, th, tw) and (c, kd, kh, kw).
+_Rank = collections.namedtuple("_Rank", "taps2 taps3 s2d k3 d2s conv_k2s2 tconv_k2s2 conv_k3 k3_input k3_warn flip")
+_RANK = {   # x.dim() - 2 -> everything of the nodes below that depends on the rank (loader / epilogue ids: of _gemm and of _wgrad)
+    2: _Rank(4, 9, LOAD_S2D_2D, LOAD_K3_2D, EPI_D2S_2D, "conv2d_k2s2", "tconv2d_k2s2", "conv2d_k3",
+             torch.nn.grad.conv2d_input, "Conv2d(k=3) input gradient", (2, 3)),
+    3: _Rank(8, 27, LOAD_S2D, LOAD_K3, EPI_D2S, "conv_k2s2", "tconv_k2s2", "conv_k3",
+             torch.nn.grad.conv3d_input, "Conv3d(k=3) input gradient", (2, 3, 4)),
+}
+
+
+def _dhw(x):
+    """(D, H, W) of a channels-first tensor; D = 1 for a 2-D one (the kernels walk a depth-1 grid)"""
+    return (1, *x.shape[2:]) if x.dim() == 4 else tuple(x.shape[2:])
+
+
 class ConvK2S2Fn(torch.autograd.Function):
-    """Conv3d(kernel 2, stride 2): space-to-depth gather fused into the GEMM's operand loads."""
+    """Conv2d / Conv3d(kernel 2, stride 2): space-to-depth gather fused into the GEMM's operand loads."""
 
     @staticmethod
     @N.capture_products
     def forward(ctx, x, w, b):
         x = x.contiguous()
-        B, C, D, H, W = x.shape
+        r = _RANK[x.dim() - 2]
+        B, C = x.shape[:2]
+        D, H, W = _dhw(x)
         O = w.shape[0]
-        Do, Ho, Wo = D // 2, H // 2, W // 2
-        y = torch.empty((B, O, Do, Ho, Wo), dtype=x.dtype, device=x.device)
-        _gemm([x], w, y, B=B, Cin=C, Vin=D * H * W, M=O, K=8 * C, Ncol=Do * Ho * Wo, bias=b, loader=LOAD_S2D,
-              Di=D, Hi=H, Wi=W, Ho=Ho, Wo=Wo, name="conv_k2s2")
+        y = torch.empty((B, O, *(s // 2 for s in x.shape[2:])), dtype=x.dtype, device=x.device)
+        Ho, Wo = H // 2, W // 2
+        _gemm([x], w, y, B=B, Cin=C, Vin=D * H * W, M=O, K=r.taps2 * C, Ncol=_vox(y), bias=b, loader=r.s2d,
+              Di=D, Hi=H, Wi=W, Ho=Ho, Wo=Wo, name=r.conv_k2s2)
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         return y
@@ -876,27 +897,29 @@ class ConvK2S2Fn(torch.autograd.Function):
     def backward(ctx, gy, g_skip=None):
         x, w = ctx.saved_tensors
         gy = gy.contiguous()
-        B, C, D, H, W = x.shape
+        r = _RANK[x.dim() - 2]
+        B, C = x.shape[:2]
+        D, H, W = _dhw(x)
         O = w.shape[0]
-        Do, Ho, Wo = D // 2, H // 2, W // 2
-        Vc = Do * Ho * Wo
+        Ho, Wo = H // 2, W // 2
+        Vc = _vox(gy)
         gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             if g_skip is not None:
                 g_skip = g_skip.contiguous()
-            # rows (ci, tap), reduction over o:  A[m][k] = w[k*(8C) + m]
-            _gemm([gy], w, gx, B=B, Cin=O, Vin=Vc, M=8 * C, K=O, Ncol=Vc, w_t=True, ldw=8 * C,
-                  epilogue=EPI_D2S, Ho=Ho, Wo=Wo, res=g_skip, name="conv_k2s2_dgrad")
+            # rows (ci, tap), reduction over o:  A[m][k] = w[k*(taps*C) + m]; the skip gradient is the epilogue's residual
+            _gemm([gy], w, gx, B=B, Cin=O, Vin=Vc, M=r.taps2 * C, K=O, Ncol=Vc, w_t=True, ldw=r.taps2 * C,
+                  epilogue=r.d2s, Ho=Ho, Wo=Wo, res=g_skip, name=r.conv_k2s2 + "_dgrad")
         gw = _GB.out_like(w)
         gb = torch.empty(O, dtype=torch.float32, device=x.device)
-        _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=8 * C, Vq=D * H * W, Ncols=Vc, gbias=gb, loader=LOAD_S2D,
-               D=D, H=H, W=W, Ho=Ho, Wo=Wo, name="wgrad_conv_k2s2")
+        _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=r.taps2 * C, Vq=D * H * W, Ncols=Vc, gbias=gb, loader=r.s2d,
+               D=D, H=H, W=W, Ho=Ho, Wo=Wo, name="wgrad_" + r.conv_k2s2)
         return gx, gw, (gb if ctx.has_bias else None)
 
 
 class SkipConvK2S2Fn(torch.autograd.Function):
-    """(x, Conv3d(k=2, s=2)(x)) as ONE node: the encoder output feeds both the skip connection and
+    """(x, Conv(k=2, s=2)(x)) as ONE node: the encoder output feeds both the skip connection and
     the next stage's down-convolution (unet.py:95-99), so its gradient is the sum of two terms that
     autograd would add in a separate full-tensor pass; here the skip gradient is the residual of the
     depth-to-space epilogue of the convolution's input-gradient kernel."""
@@ -916,18 +939,20 @@ class SkipConvK2S2Fn(torch.autograd.Function):
 
 
 class TConvK2S2Fn(torch.autograd.Function):
-    """ConvTranspose3d(kernel 2, stride 2): GEMM with (o, tap) rows + depth-to-space epilogue."""
+    """ConvTranspose2d / ConvTranspose3d(kernel 2, stride 2): GEMM with (o, tap) rows + depth-to-space epilogue."""
 
     @staticmethod
     @N.capture_products
     def forward(ctx, x, w, b):
         x = x.contiguous()
-        B, C, D, H, W = x.shape
+        r = _RANK[x.dim() - 2]
+        B, C = x.shape[:2]
+        H, W = x.shape[-2:]
         O = w.shape[1]
-        y = torch.empty((B, O, 2 * D, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
-        V = D * H * W
-        _gemm([x], w, y, B=B, Cin=C, Vin=V, M=8 * O, K=C, Ncol=V, w_t=True, ldw=8 * O, bias=b,
-              epilogue=EPI_D2S, Ho=H, Wo=W, name="tconv_k2s2")
+        y = torch.empty((B, O, *(2 * s for s in x.shape[2:])), dtype=x.dtype, device=x.device)
+        V = _vox(x)
+        _gemm([x], w, y, B=B, Cin=C, Vin=V, M=r.taps2 * O, K=C, Ncol=V, w_t=True, ldw=r.taps2 * O, bias=b,
+              epilogue=r.d2s, Ho=H, Wo=W, name=r.tconv_k2s2)
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         return y
@@ -937,22 +962,25 @@ class TConvK2S2Fn(torch.autograd.Function):
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
         gy = gy.contiguous()
-        B, C, D, H, W = x.shape
+        r = _RANK[x.dim() - 2]
+        B, C = x.shape[:2]
+        H, W = x.shape[-2:]
+        Df, Hf, Wf = _dhw(gy)   # the fine grid
         O = w.shape[1]
-        V = D * H * W
+        V = _vox(x)
         gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            # GX[ci, coarse] = Σ_{o,tap} w[ci, o, tap] · GY[o, fine]: a k2s2 "conv" of gy with w as [C][8O]
-            _gemm([gy], w, gx, B=B, Cin=O, Vin=8 * V, M=C, K=8 * O, Ncol=V, loader=LOAD_S2D,
-                  Di=2 * D, Hi=2 * H, Wi=2 * W, Ho=H, Wo=W, name="tconv_k2s2_dgrad")
+            # GX[ci, coarse] = Σ_{o,tap} w[ci, o, tap] · GY[o, fine]: a k2s2 "conv" of gy with w as [C][taps*O]
+            _gemm([gy], w, gx, B=B, Cin=O, Vin=r.taps2 * V, M=C, K=r.taps2 * O, Ncol=V, loader=r.s2d,
+                  Di=Df, Hi=Hf, Wi=Wf, Ho=H, Wo=W, name=r.tconv_k2s2 + "_dgrad")
         gw = _GB.out_like(w)
         # GW[ci][(o,tap)] = Σ X[ci][n] · GY[o][fine(n,tap)]
-        _wgrad(x, [gy], gw, B=B, M=C, Cin=O, K=8 * O, Vq=8 * V, Ncols=V, loader=LOAD_S2D, D=2 * D, H=2 * H,
-               W=2 * W, Ho=H, Wo=W, name="wgrad_tconv_k2s2")
+        _wgrad(x, [gy], gw, B=B, M=C, Cin=O, K=r.taps2 * O, Vq=r.taps2 * V, Ncols=V, loader=r.s2d, D=Df, H=Hf,
+               W=Wf, Ho=H, Wo=W, name="wgrad_" + r.tconv_k2s2)
         gb = None
         if ctx.has_bias:
-            Vf = 8 * V
+            Vf = r.taps2 * V
             gb = torch.empty(O, dtype=torch.float32, device=x.device)
             part = torch.empty(B * N.lib().fz_rowsum_chunks(Vf) * O, dtype=torch.float32, device=x.device)
             with torch.cuda.device(x.device), _finish_scope(part, gb):
@@ -963,8 +991,8 @@ class TConvK2S2Fn(torch.autograd.Function):
 
 
 class ConvK3Fn(torch.autograd.Function):
-    """Conv3d(kernel 3, padding 1) — the stem (C_in = 4): direct implicit-GEMM kernels
-    (csrc/conv3.hip); shapes outside them use the generic tap loaders of the GEMM family."""
+    """Conv2d / Conv3d(kernel 3, padding 1) — the stem: in 3-D with C_in = 4, direct implicit-GEMM kernels
+    (csrc/conv3.hip); 2-D, and 3-D shapes outside them, use the generic tap loaders of the GEMM family."""
 
     _fz_acts = (0, 3)   # inputs that are activations (see _param_sinks_ok); every other input is a parameter
 
@@ -974,12 +1002,14 @@ class ConvK3Fn(torch.autograd.Function):
         # pro: as UpCatLinearFn.forward — the consuming block's (ln1 weight, ln1 bias, eps, in_proj weight); the node then returns
         # (y, t, statistics), the last two formed in the same launch and not differentiable here
         x = x.contiguous()
-        B, C, D, H, W = x.shape
+        r = _RANK[x.dim() - 2]
+        B, C = x.shape[:2]
+        D, H, W = _dhw(x)
         O = w.shape[0]
         V = D * H * W
-        y = torch.empty((B, O, D, H, W), dtype=x.dtype, device=x.device)
+        y = torch.empty((B, O, *x.shape[2:]), dtype=x.dtype, device=x.device)
         ctx.npro = 0 if pro is None else 1
-        if C * 27 * 64 * 4 <= 65536:
+        if x.dim() == 5 and C * 27 * 64 * 4 <= 65536:   # the stem kernel: 3-D only
             bp = None
             if pro is not None:
                 ln_w, ln_b, eps, w_in = pro
@@ -996,8 +1026,8 @@ class ConvK3Fn(torch.autograd.Function):
         elif pro is not None:
             raise RuntimeError("ConvK3Fn: a block prologue needs the stem kernel (callers check conv3_prologue_ok)")
         else:
-            _gemm([x], w, y, B=B, Cin=C, Vin=V, M=O, K=27 * C, Ncol=V, bias=b, loader=LOAD_K3, Di=D, Hi=H, Wi=W,
-                  name="conv_k3")
+            _gemm([x], w, y, B=B, Cin=C, Vin=V, M=O, K=r.taps3 * C, Ncol=V, bias=b, loader=r.k3, Di=D, Hi=H, Wi=W,
+                  name=r.conv_k3)
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         if pro is not None:
@@ -1013,24 +1043,28 @@ class ConvK3Fn(torch.autograd.Function):
         if gy is None:
             gy = torch.zeros((x.shape[0], w.shape[0], *x.shape[2:]), dtype=x.dtype, device=x.device)
         gy = gy.contiguous()
-        B, C, D, H, W = x.shape
+        r = _RANK[x.dim() - 2]
+        B, C = x.shape[:2]
+        D, H, W = _dhw(x)
         O = w.shape[0]
         V = D * H * W
         gx = None
         if ctx.needs_input_grad[0]:
             # not on the training path (the stem's input is data): the adjoint is the same k3 correlation with the
-            # channel-transposed, spatially flipped filters — the generic tap loader of the GEMM family
+            # channel-transposed, spatially flipped filters — the generic tap loader of the GEMM family.
+            # The W % 4 gate changes nothing in 2-D: fz_gemm refuses LOAD_K3_2D with Wi & 3 (csrc/gemm.hip, the LOAD_K3_2D
+            # check), so no 2-D forward with W % 4 != 0 ever reached this backward.
             if O % 2 == 0 and W % 4 == 0:
-                wt = torch.flip(w, dims=(2, 3, 4)).transpose(0, 1).contiguous()
+                wt = torch.flip(w, dims=r.flip).transpose(0, 1).contiguous()
                 gx = torch.empty_like(x)
-                _gemm([gy], wt, gx, B=B, Cin=O, Vin=V, M=C, K=27 * O, Ncol=V, loader=LOAD_K3, Di=D, Hi=H, Wi=W,
-                      name="conv_k3_dgrad")
+                _gemm([gy], wt, gx, B=B, Cin=O, Vin=V, M=C, K=r.taps3 * O, Ncol=V, loader=r.k3, Di=D, Hi=H, Wi=W,
+                      name=r.conv_k3 + "_dgrad")
             else:
-                _warn_composed("Conv3d(k=3) input gradient", x)
-                gx = torch.nn.grad.conv3d_input(x.shape, w, gy, padding=1)
+                _warn_composed(r.k3_warn, x)
+                gx = r.k3_input(x.shape, w, gy, padding=1)
         gw = _GB.out_like(w)
         gb = torch.empty(O, dtype=torch.float32, device=x.device)
-        if W % 32 == 0 and 27 * C <= 128:
+        if x.dim() == 5 and W % 32 == 0 and 27 * C <= 128:   # the direct weight-gradient kernel: 3-D only
             lib = N.lib()
             nchunk = lib.fz_conv3_wgrad_chunks(B, D, H, W)
             K = 27 * C
@@ -1052,162 +1086,9 @@ class ConvK3Fn(torch.autograd.Function):
                                cols=B * V, flops=2 * B * V * K * O)
             N.check(rc, "fz_conv3_wgrad")
         else:
-            _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=27 * C, Vq=V, Ncols=V, gbias=gb, loader=LOAD_K3, D=D, H=H, W=W,
-                   name="wgrad_conv_k3")
+            _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=r.taps3 * C, Vq=V, Ncols=V, gbias=gb, loader=r.k3, D=D, H=H, W=W,
+                   name="wgrad_" + r.conv_k3)
         return (gx, gw, (gb if ctx.has_bias else None), None)[:len(ctx.needs_input_grad)]   # (one per argument actually passed)
-
-
-
-# ---- the same convolutions of a 2-D U-shape (Conv2d / ConvTranspose2d; convs.Conv2d, convs.ConvTranspose2d) -------------
-# Tap orders (weights are used in place, no packing pass): k2s2 rows / columns k = (c, th, tw) = c*4 + th*2 + tw, i.e. the
-# row-major flattening of Conv2d's (O, C, 2, 2) weight and ConvTranspose2d's (C, O, 2, 2) weight; k3p1 k = (c, kh, kw) =
-# c*9 + kh*3 + kw, the flattening of (O, C, 3, 3).  DESIGN.md §3 "2-D tap geometries".
-class ConvK2S2Fn2d(torch.autograd.Function):
-    """Conv2d(kernel 2, stride 2): 2-D space-to-depth gather fused into the GEMM's operand loads (LOAD_S2D_2D)."""
-
-    @staticmethod
-    @N.capture_products
-    def forward(ctx, x, w, b):
-        x = x.contiguous()
-        B, C, H, W = x.shape
-        O = w.shape[0]
-        Ho, Wo = H // 2, W // 2
-        y = torch.empty((B, O, Ho, Wo), dtype=x.dtype, device=x.device)
-        _gemm([x], w, y, B=B, Cin=C, Vin=H * W, M=O, K=4 * C, Ncol=Ho * Wo, bias=b, loader=LOAD_S2D_2D,
-              Di=1, Hi=H, Wi=W, Ho=Ho, Wo=Wo, name="conv2d_k2s2")
-        ctx.save_for_backward(x, w)
-        ctx.has_bias = b is not None
-        return y
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, gy, g_skip=None):
-        x, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        B, C, H, W = x.shape
-        O = w.shape[0]
-        Ho, Wo = H // 2, W // 2
-        Vc = Ho * Wo
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            if g_skip is not None:
-                g_skip = g_skip.contiguous()
-            # rows (ci, th, tw), reduction over o:  A[m][k] = w[k*(4C) + m]; the skip gradient is the epilogue's residual
-            _gemm([gy], w, gx, B=B, Cin=O, Vin=Vc, M=4 * C, K=O, Ncol=Vc, w_t=True, ldw=4 * C,
-                  epilogue=EPI_D2S_2D, Ho=Ho, Wo=Wo, res=g_skip, name="conv2d_k2s2_dgrad")
-        gw = _GB.out_like(w)
-        gb = torch.empty(O, dtype=torch.float32, device=x.device)
-        _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=4 * C, Vq=H * W, Ncols=Vc, gbias=gb, loader=QL_S2D_2D,
-               D=1, H=H, W=W, Ho=Ho, Wo=Wo, name="wgrad_conv2d_k2s2")
-        return gx, gw, (gb if ctx.has_bias else None)
-
-
-class SkipConvK2S2Fn2d(torch.autograd.Function):
-    """(x, Conv2d(k=2, s=2)(x)) as ONE node (SkipConvK2S2Fn in 2-D)."""
-
-    @staticmethod
-    @N.capture_products
-    def forward(ctx, x, w, b):
-        y = ConvK2S2Fn2d.forward(ctx, x, w, b)
-        return x.view_as(x), y
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, g_skip, gy):
-        if gy is None:  # the down path took no part in the loss
-            return g_skip, None, None
-        return ConvK2S2Fn2d.backward(ctx, gy, g_skip=g_skip)
-
-
-class TConvK2S2Fn2d(torch.autograd.Function):
-    """ConvTranspose2d(kernel 2, stride 2): GEMM with (o, th, tw) rows + 2-D depth-to-space epilogue (EPI_D2S_2D)."""
-
-    @staticmethod
-    @N.capture_products
-    def forward(ctx, x, w, b):
-        x = x.contiguous()
-        B, C, H, W = x.shape
-        O = w.shape[1]
-        y = torch.empty((B, O, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
-        V = H * W
-        _gemm([x], w, y, B=B, Cin=C, Vin=V, M=4 * O, K=C, Ncol=V, w_t=True, ldw=4 * O, bias=b,
-              epilogue=EPI_D2S_2D, Ho=H, Wo=W, name="tconv2d_k2s2")
-        ctx.save_for_backward(x, w)
-        ctx.has_bias = b is not None
-        return y
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        B, C, H, W = x.shape
-        O = w.shape[1]
-        V = H * W
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            # GX[ci, coarse] = Σ_{o,th,tw} w[ci, o, th, tw] · GY[o, fine]: a 2-D k2s2 "conv" of gy with w as [C][4O]
-            _gemm([gy], w, gx, B=B, Cin=O, Vin=4 * V, M=C, K=4 * O, Ncol=V, loader=LOAD_S2D_2D,
-                  Di=1, Hi=2 * H, Wi=2 * W, Ho=H, Wo=W, name="tconv2d_k2s2_dgrad")
-        gw = _GB.out_like(w)
-        # GW[ci][(o,th,tw)] = Σ X[ci][n] · GY[o][fine(n,th,tw)]
-        _wgrad(x, [gy], gw, B=B, M=C, Cin=O, K=4 * O, Vq=4 * V, Ncols=V, loader=QL_S2D_2D, D=1, H=2 * H,
-               W=2 * W, Ho=H, Wo=W, name="wgrad_tconv2d_k2s2")
-        gb = None
-        if ctx.has_bias:
-            Vf = 4 * V
-            gb = torch.empty(O, dtype=torch.float32, device=x.device)
-            part = torch.empty(B * N.lib().fz_rowsum_chunks(Vf) * O, dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device), _finish_scope(part, gb):
-                rc = N.lib().fz_rowsum(gy.data_ptr(), part.data_ptr(), gb.data_ptr(), B, O, Vf, N.act_dtype(gy),
-                                       N.stream_ptr(x))
-            N.check(rc, "fz_rowsum")
-        return gx, gw, gb
-
-
-class ConvK3Fn2d(torch.autograd.Function):
-    """Conv2d(kernel 3, padding 1) — the stem of a 2-D U-shape: the 3x3 tap loader of the GEMM family (LOAD_K3_2D)."""
-
-    @staticmethod
-    @N.capture_products
-    def forward(ctx, x, w, b):
-        x = x.contiguous()
-        B, C, H, W = x.shape
-        O = w.shape[0]
-        V = H * W
-        y = torch.empty((B, O, H, W), dtype=x.dtype, device=x.device)
-        _gemm([x], w, y, B=B, Cin=C, Vin=V, M=O, K=9 * C, Ncol=V, bias=b, loader=LOAD_K3_2D, Di=1, Hi=H, Wi=W,
-              name="conv2d_k3")
-        ctx.save_for_backward(x, w)
-        ctx.has_bias = b is not None
-        return y
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        B, C, H, W = x.shape
-        O = w.shape[0]
-        V = H * W
-        gx = None
-        if ctx.needs_input_grad[0]:
-            # the adjoint is the same 3x3 correlation with the channel-transposed, spatially flipped filters
-            if O % 2 == 0:
-                wt = torch.flip(w, dims=(2, 3)).transpose(0, 1).contiguous()
-                gx = torch.empty_like(x)
-                _gemm([gy], wt, gx, B=B, Cin=O, Vin=V, M=C, K=9 * O, Ncol=V, loader=LOAD_K3_2D, Di=1, Hi=H, Wi=W,
-                      name="conv2d_k3_dgrad")
-            else:
-                _warn_composed("Conv2d(k=3) input gradient", x)
-                gx = torch.nn.grad.conv2d_input(x.shape, w, gy, padding=1)
-        gw = _GB.out_like(w)
-        gb = torch.empty(O, dtype=torch.float32, device=x.device)
-        _wgrad(gy, [x], gw, B=B, M=O, Cin=C, K=9 * C, Vq=V, Ncols=V, gbias=gb, loader=QL_K3_2D, D=1, H=H, W=W,
-               name="wgrad_conv2d_k3")
-        return gx, gw, (gb if ctx.has_bias else None)
 
 
 # ---- public dispatchers (device → native, CPU → composed ATen) ---------------------------------------

@@ -110,7 +110,7 @@ def test_tap_orders_and_weight_packing_match_conv2d_in_float64():
     w3 = torch.randn(O, C, 3, 3, dtype=torch.float64)
     y = (w3.reshape(O, 9 * C) @ k3_rows).reshape(B, O, H, W)
     torch.testing.assert_close(y, F.conv2d(x, w3, padding=1), rtol=1e-12, atol=1e-12)
-    # its input gradient: the same loader on gy with the flipped, channel-transposed filters (ConvK3Fn2d.backward)
+    # its input gradient: the same loader on gy with the flipped, channel-transposed filters (ConvK3Fn.backward)
     gy = torch.randn(B, O, H, W, dtype=torch.float64)
     wt = torch.flip(w3, dims=(2, 3)).transpose(0, 1).reshape(C, 9 * O)
     gx = (wt @ _k3(gy)).reshape(B, C, H, W)

@@ -144,7 +144,7 @@ def test_skip_fork_adds_the_skip_gradient_in_the_epilogue():
     m = m.to(DEV)
     xd = x.to(DEV).requires_grad_(True)
     skip, y = m.forward_fork(xd)
-    assert type(y.grad_fn).__name__.startswith("SkipConvK2S2Fn2d")
+    assert type(y.grad_fn).__name__.startswith("SkipConvK2S2Fn")
     (gx,) = torch.autograd.grad([skip, y], [xd], [gs.to(DEV), gy.to(DEV)])
     P.close("fork dx", gx, ref[1] + gs.double())
     P.close("fork y", y, ref[0])

@@ -12,6 +12,7 @@ from .nmf import (NMF, SVD, BCDSolver, Compose, CoordinateDescent, FastMultiplic
                   RandomInit, SemiMultiplicativeUpdate, SVDInit, WeightedMultiplicativeUpdate, relative_error)
 from .layers import MLP, LayerNorm, Linear, PosEmbed, PositionalEmbedding
 from .convs import Conv2d, Conv3d, ConvTranspose2d, ConvTranspose3d
+from .instance_norm import InstanceNorm1d, InstanceNorm2d, InstanceNorm3d, convert_instance_norm, instance_norm
 from .blocks import FactMixer, FactorizerBlock, FactorizerStage
 from .losses import DiceCELoss, dice_bce_loss, dice_ce_loss
 from .metrics import (DiceMetric, HausdorffDistanceMetric, dice_metric, discretize, hausdorff_distance, mask_edges,

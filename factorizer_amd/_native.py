@@ -339,6 +339,11 @@ _SIGS.update({
     "fz_vol_restore": ([_c.POINTER(_vp), _i, _i, _i, _c.POINTER(VolGeom), _f, _c.POINTER(_c.c_ubyte), _vp, _vp], _i),
     "fz_vol_respace": ([_vp, _i, _vp, _i, _vp, _i, _vp, _c.POINTER(RespaceGeom), _i, _vp], _i),
     "fz_vol_unspace": ([_c.POINTER(_vp), _i, _i, _i, _c.POINTER(RespaceGeom), _i, _i, _f, _vp, _vp], _i),
+    "fz_inorm_one_pass_max": ([], _i),
+    "fz_inorm_chunks": ([_i64], _i),
+    "fz_inorm_workspace_bytes": ([_i64, _i64], _i64),
+    "fz_inorm_fwd": ([_vp] * 5 + [_i64, _i, _i64, _c.c_double, _i, _vp, _vp], _i),
+    "fz_inorm_bwd": ([_vp] * 7 + [_i64, _i, _i64, _i, _vp, _vp], _i),
 })
 SEG_F32, SEG_BF16, SEG_U8 = 0, 1, 2   # include/factorizer_hip.h: FZ_SEG_* element kinds of fz_seg_counts
 VOL_F32, VOL_BF16, VOL_U8, VOL_I16 = 0, 1, 2, 3   # include/factorizer_hip.h: FZ_VOL_* element kinds

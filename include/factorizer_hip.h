@@ -907,6 +907,28 @@ int fz_vol_respace(const float* image, int C, void* out, int out_kind, const uin
 int fz_vol_unspace(const void* const* logits, int K, int kind, int C, const fz_respace_geom* geom, int sigmoid, int discretize,
                    float threshold, void* result, fz_stream_t stream);
 
+/* ---- instance norm of channels-first activations (csrc/inorm.hip, csrc/inorm_core.h; semantics:
+ * factorizer_amd/instance_norm.py) ----
+ * The block norm of the Deconver bundles (deconver.py:50-66 norm1 / norm2 and :129-138 Stem with norm: nn.InstanceNorm3d /
+ * nn.InstanceNorm2d).  x, y, gy, gx: (B, C, *S) contiguous of act_dtype, seen as P = B C planes of V elements, element-aligned
+ * (any storage offset, any V); weight, bias (C) fp32 or NULL (1 and 0); stats (P, 2) float64 = (mean, 1 / sqrt(var + eps)) per
+ * plane, written by the forward and read by the backward.  All arithmetic is float64, one rounding per stored element:
+ *   mean = x0 + Σd / V, var = max(Σd² / V − (Σd / V)², 0) with d = x − x0, x0 the plane's first element (biased variance);
+ *   y = (x − mean) rstd γ_c + β_c;   gx = (g γ_c − a − x̂ b) rstd with x̂ = (x − mean) rstd, a = γ_c Σg / V, b = γ_c Σg x̂ / V;
+ *   gbias_c = Σ_b Σ_v g, gweight_c = Σ_b Σ_v g x̂ (either may be NULL), per-plane totals summed over b in index order.
+ * No atomics: every sum has a fixed order that depends on V alone, so results repeat bit for bit and a plane's result does not
+ * depend on the other planes or on its address.  Planes of V <= fz_inorm_one_pass_max() take one launch each way; larger ones
+ * two over fz_inorm_chunks(V) workgroups per plane; gweight / gbias add one.  workspace: fz_inorm_workspace_bytes(P, V) bytes,
+ * 8-byte aligned, scratch of one call (-1: P < 1, V < 1 or too large).  V < 1, P < 1: FZ_E_ARG; act_dtype outside FZ_STORE_*:
+ * FZ_E_UNSUPPORTED; P not a multiple of C, V >= 2^31, 2^24 or more workgroups (P fz_inorm_chunks(V)): FZ_E_SHAPE — all before anything touches the device. */
+int fz_inorm_one_pass_max(void);
+int fz_inorm_chunks(int64_t V);
+int64_t fz_inorm_workspace_bytes(int64_t P, int64_t V);
+int fz_inorm_fwd(const void* x, const float* weight, const float* bias, void* y, double* stats, int64_t P, int C, int64_t V,
+                 double eps, int act_dtype, void* workspace, fz_stream_t stream);
+int fz_inorm_bwd(const void* x, const void* gy, const float* weight, const double* stats, void* gx, float* gweight,
+                 float* gbias, int64_t P, int C, int64_t V, int act_dtype, void* workspace, fz_stream_t stream);
+
 /* ---- AdamW over one flat buffer (torch.optim.AdamW of the training recipe,
  * model_zoo/factorizer_brats23/configs/train.yaml:72-76).  step >= 1 is the 1-based update count;
  * grad_scale multiplies the gradient first (1/world after a summed all-reduce). */

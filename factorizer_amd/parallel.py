@@ -71,10 +71,14 @@ class FlatGradSync:
         self._launched = [False] * len(self.buckets)
         self.active = self.world > 1 or (force_collectives and dist.is_initialized())
         self.overlap = overlap and self.active
+        self._hooks = []   # (held here: pointwise keeps only weak references to an owner's hooks)
         if self.overlap:
+            from . import pointwise as _PW
             for bi, b in enumerate(self.buckets):
+                hook = _PW.owner_hook(self._make_hook(bi))   # flushes before it reads a gradient: its parameters may still defer
+                self._hooks.append(hook)
                 for p in b["params"]:
-                    p.register_post_accumulate_grad_hook(self._make_hook(bi))
+                    p.register_post_accumulate_grad_hook(hook)
 
     # ---- parameters / buffers start identical on every rank (incl. NMF init.u0/v0) ----
     def broadcast_state(self, src: int = 0):

@@ -481,11 +481,21 @@ class _Defer:
     without zero_grad (gradient accumulation: autograd then ADDS to .grad while the backward runs) is never deferred.
     A returned gradient buffer stays unwritten until the flush, so a node defers only when nothing can read its parameter
     gradients before the backward ends — `_param_sinks_ok` decides that per node from the autograd graph (each one must go,
-    through views at most, straight to the AccumulateGrad of an owned leaf that has no gradient yet, no tensor hooks, and is
-    used once in this backward; no double backward).  Everything else — a weight that is computed from a parameter (the
-    padded stem weight of odd channel counts), a parameter used twice, `p.register_hook`, `create_graph=True`, a model the
-    owner does not cover — runs its finishes at once, as do sites whose results feed a torch op inside the backward
-    (`_no_defer`).  Post-accumulate hooks other than the owner's must call `flush_finishes()` before they read `.grad`.
+    through views at most, straight to the AccumulateGrad of an owned leaf that has no gradient yet, no tensor hooks, no
+    post-accumulate-grad hook but the owner's, and is used once in this backward; no double backward).  Everything else — a
+    weight that is computed from a parameter (the padded stem weight of odd channel counts), a parameter used twice,
+    `p.register_hook`, `p.register_post_accumulate_grad_hook`, `create_graph=True`, a model the owner does not cover — runs its
+    finishes at once, as do sites whose results feed a torch op inside the backward (`_no_defer`).
+    Index rule: `needs_input_grad` and a Function's `_fz_acts` count the ARGUMENTS of `apply`, `ctx.next_functions` counts its
+    TENSOR arguments only (a float eps, a string act, a dict cfg, a tuple or a None takes no entry).  Every forward records
+    the map between the two (`_fwd`: `ctx._fz_slots`); the guard indexes `next_functions` through it and refuses — never
+    raises — when the map is missing or does not fit the node.
+    Hook rule: a post-accumulate-grad hook runs as soon as the engine has assigned `.grad`, i.e. before the flush, so a
+    parameter that carries one is not deferred — unless every such hook was registered by the arming owner through
+    `owner_hook` (FlatGradSync's bucket hooks call `flush_finishes()` before they touch a gradient).  Hooks put on the
+    AccumulateGrad NODE itself (`node.register_hook` / `register_prehook`) cannot be refused: torch exposes no accessor for
+    them, and probing by registering a hook of one's own would cost a Python call per parameter and backward; they see the
+    gradient tensor before the flush and must call `flush_finishes()` before they read it.
     The arithmetic is the same either way (bitwise)."""
     enabled = False
     armed = False
@@ -498,6 +508,7 @@ class _Defer:
     flushed = 0     # finishes run through flushes so far (tests)
     flushes = 0
     refused = 0     # backward nodes that ran their finishes at once because `_param_sinks_ok` said no (tests)
+    own_hooks = weakref.WeakSet()   # post-accumulate-grad hooks installed by an arming owner itself (`owner_hook`)
 
 
 def defer_finishes(flag: bool = True):
@@ -592,38 +603,89 @@ _VIEW_NODES = frozenset(("ViewBackward0", "ReshapeAliasBackward0", "UnsafeViewBa
                          "SqueezeBackward1", "AliasBackward0", "DetachBackward0"))
 
 
+def _fwd(fn):
+    """decorator of every forward below: N.capture_products + the map from forward-argument position to tensor-input
+    position (`ctx._fz_slots`; -1 for an argument that is no tensor).  Autograd gives a node one `next_functions` entry per
+    TENSOR argument of `apply` — a float, a string, a dict, a tuple or a None takes none — so `_param_sinks_ok` must not index
+    `next_functions` with the argument position.  (The outermost forward of a node sets the map: LinearFn and SkipConvK2S2Fn
+    hand their ctx on to another Function's forward.)"""
+    import functools
+    inner = N.capture_products(fn)
+
+    @functools.wraps(fn)
+    def wrapper(ctx, *a, **kw):
+        if getattr(ctx, "_fz_slots", None) is None:
+            k, slots = 0, []
+            for v in a:
+                if isinstance(v, torch.Tensor):
+                    slots.append(k)
+                    k += 1
+                else:
+                    slots.append(-1)
+            ctx._fz_slots = tuple(slots)
+        return inner(ctx, *a, **kw)
+    return wrapper
+
+
+def owner_hook(hook):
+    """An arming owner registers here the post-accumulate-grad hooks it installs on its own parameters (FlatGradSync's bucket
+    hooks, which flush before they read a gradient): `_param_sinks_ok` lets a parameter that carries only such hooks defer."""
+    _Defer.own_hooks.add(hook)
+    return hook
+
+
+def _own_hook(hook) -> bool:
+    try:
+        return hook in _Defer.own_hooks
+    except TypeError:   # an unhashable callable is nobody's registered hook
+        return False
+
+
+def _refuse(ctx, why):
+    if os.environ.get("FZ_DEFER_DEBUG"):
+        print(f"[defer] {type(ctx).__name__}: {why}", flush=True)
+    return False
+
+
 def _param_sinks_ok(ctx) -> bool:
     """May this backward node leave its parameter gradients unwritten until the end of the backward?  Inputs listed in the
     Function's `_fz_acts` (default: input 0) are activations — their gradients are complete when the node returns; every other
     input that needs a gradient gets it from a finish job and must lead, through views at most, to the AccumulateGrad of an
-    owned, gradient-less, hook-less leaf that no earlier node of this backward has served."""
+    owned, gradient-less, hook-less leaf that no earlier node of this backward has served.  `_fz_acts` and `needs_input_grad`
+    count forward ARGUMENTS, `next_functions` counts tensor inputs: `ctx._fz_slots` (`_fwd`) maps one to the other, and a node
+    whose map is missing or does not fit its `next_functions` runs its finishes at once."""
     d = _Defer
     if torch.is_grad_enabled():          # create_graph=True: the gradients are graph inputs of a double backward
         return False
     acts = getattr(getattr(ctx, "_forward_cls", None), "_fz_acts", (0,))   # (a backward ctx is not an instance of the Function class)
-    for i, need in enumerate(ctx.needs_input_grad):
+    slots = getattr(ctx, "_fz_slots", None)
+    need_grad = ctx.needs_input_grad
+    nexts = ctx.next_functions
+    if slots is None or len(slots) != len(need_grad) or max(slots, default=-1) + 1 != len(nexts):
+        return _refuse(ctx, f"argument map {slots} does not fit {len(need_grad)} arguments / {len(nexts)} tensor inputs")
+    for i, need in enumerate(need_grad):
         if not need or i in acts:
             continue
-        fn = ctx.next_functions[i][0]
+        if slots[i] < 0:
+            return _refuse(ctx, f"input {i} needs a gradient and is no tensor")
+        fn = nexts[slots[i]][0]
         while fn is not None and type(fn).__name__ in _VIEW_NODES:
             fn = fn.next_functions[0][0]
         if fn is None or type(fn).__name__ != "AccumulateGrad":
-            if os.environ.get("FZ_DEFER_DEBUG"):
-                print(f"[defer] {type(ctx).__name__}: input {i} sink {type(fn).__name__}", flush=True)
-            return False
+            return _refuse(ctx, f"input {i} sink {type(fn).__name__}")
         v = fn.variable
         vid = id(v)
         if vid not in d.owned or v.grad is not None or v._backward_hooks:
-            if os.environ.get("FZ_DEFER_DEBUG"):
-                print(f"[defer] {type(ctx).__name__}: input {i} {tuple(v.shape)} owned={vid in d.owned} grad={v.grad is not None} hooks={bool(v._backward_hooks)}", flush=True)
-            return False
+            return _refuse(ctx, f"input {i} {tuple(v.shape)} owned={vid in d.owned} grad={v.grad is not None} hooks={bool(v._backward_hooks)}")
+        post = v._post_accumulate_grad_hooks
+        if post and not all(_own_hook(h) for h in post.values()):
+            # a hook that runs right after the engine assigns .grad would read the unwritten buffer
+            return _refuse(ctx, f"input {i} {tuple(v.shape)} has a post-accumulate-grad hook that is not the owner's")
         if vid in d.seen:
-            if os.environ.get("FZ_DEFER_DEBUG"):
-                print(f"[defer] {type(ctx).__name__}: input {i} {tuple(v.shape)} already served in this backward", flush=True)
             # second use of a parameter in one graph: the engine is about to ADD this node's gradient to the first one's —
             # which must therefore be complete now
             flush_finishes()
-            return False
+            return _refuse(ctx, f"input {i} {tuple(v.shape)} already served in this backward")
         d.seen.add(vid)
     return True
 
@@ -679,7 +741,7 @@ def _head_rows_reduce(part, rows, w2, M, like):
 # ---- LayerNorm → Linear → [ReLU] -----------------------------------------------------------
 class LNLinearFn(torch.autograd.Function):
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x, ln_w, ln_b, eps, w, b, act):
         x = x.contiguous()
         B, C = x.shape[:2]
@@ -721,7 +783,7 @@ class ActLinearResFn(torch.autograd.Function):
     _fz_acts = (0, 3)   # inputs that are activations (see _param_sinks_ok); every other input is a parameter
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, z, w, b, res, bact):
         z = z.contiguous()
         B, C = z.shape[:2]
@@ -772,7 +834,7 @@ class CatLinearFn(torch.autograd.Function):
     _fz_acts = (0, 1)   # inputs that are activations (see _param_sinks_ok); every other input is a parameter
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x1, x2, w, b):
         x1, x2 = x1.contiguous(), x2.contiguous()
         B, C1 = x1.shape[:2]
@@ -815,7 +877,7 @@ class CatLinearFn(torch.autograd.Function):
 
 class LinearFn(torch.autograd.Function):
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x, w, b):
         return ActLinearResFn.forward(ctx, x, w, b, None, "none")
 
@@ -828,7 +890,7 @@ class LinearFn(torch.autograd.Function):
 # ---- standalone LayerNorm -------------------------------------------------------------------------
 class LayerNormFn(torch.autograd.Function):
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x, w, b, eps):
         x = x.contiguous()
         B, C = x.shape[:2]
@@ -877,7 +939,7 @@ class ConvK2S2Fn(torch.autograd.Function):
     """Conv2d / Conv3d(kernel 2, stride 2): space-to-depth gather fused into the GEMM's operand loads."""
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x, w, b):
         x = x.contiguous()
         r = _RANK[x.dim() - 2]
@@ -925,7 +987,7 @@ class SkipConvK2S2Fn(torch.autograd.Function):
     depth-to-space epilogue of the convolution's input-gradient kernel."""
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x, w, b):
         y = ConvK2S2Fn.forward(ctx, x, w, b)
         return x.view_as(x), y
@@ -942,7 +1004,7 @@ class TConvK2S2Fn(torch.autograd.Function):
     """ConvTranspose2d / ConvTranspose3d(kernel 2, stride 2): GEMM with (o, tap) rows + depth-to-space epilogue."""
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x, w, b):
         x = x.contiguous()
         r = _RANK[x.dim() - 2]
@@ -997,7 +1059,7 @@ class ConvK3Fn(torch.autograd.Function):
     _fz_acts = (0, 3)   # inputs that are activations (see _param_sinks_ok); every other input is a parameter
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x, w, b, pro=None):
         # pro: as UpCatLinearFn.forward — the consuming block's (ln1 weight, ln1 bias, eps, in_proj weight); the node then returns
         # (y, t, statistics), the last two formed in the same launch and not differentiable here
@@ -1164,7 +1226,7 @@ class UpCatLinearFn(torch.autograd.Function):
     _fz_acts = (0, 1, 6)   # inputs that are activations (see _param_sinks_ok); every other input is a parameter
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, skip, deep, w_t, b_t, w_ad, b_ad, pro=None):
         # pro = (ln1 weight, ln1 bias, eps, in_proj weight) of the FactorizerBlock that consumes the output: the node then also
         # returns t = relu(in_proj(LN1(out))) and the LayerNorm statistics, formed in the same launch (not differentiable here:
@@ -1408,7 +1470,7 @@ class FactorizerBlockFn(torch.autograd.Function):
     _fz_acts = (0, 4, 5, 14, 15, 16, 17, 18)   # inputs that are activations (see _param_sinks_ok); every other input is a parameter
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, x, n1w, n1b, win, u0, v0, wout, bout, n2w, n2b, w1, b1, w2, b2, cfg, head_w=None, head_b=None,
                 t_pre=None, st_pre=None):
         # t_pre / st_pre: t = relu(in_proj(LN1(x))) and the LayerNorm statistics already formed by the launch that produced x
@@ -1678,7 +1740,7 @@ class HeadOfBlockFn(torch.autograd.Function):
     _fz_acts = (0, 3)   # inputs that are activations (see _param_sinks_ok); every other input is a parameter
 
     @staticmethod
-    @N.capture_products
+    @_fwd
     def forward(ctx, y, w, b, logits):
         ctx.save_for_backward(y, w)
         ctx.has_bias, ctx.wshape = b is not None, w.shape

@@ -161,14 +161,17 @@ def test_num_heads_8_block_m_not_8():
         gy = torch.rand_like(x)
         xc = x.clone().requires_grad_(True)
         yc = blk(xc)                                    # composed CPU path (pinned against the reference goldens)
-        (gxc,) = torch.autograd.grad(yc, xc, gy)
+        names = [n for n, _ in blk.named_parameters()]
+        gxc, *gpc = torch.autograd.grad(yc, [xc, *blk.parameters()], gy)
         blk = blk.to(DEV)
         xd = x.to(DEV).requires_grad_(True)
         n0 = _native.launch_count()
         with warnings.catch_warnings():
             warnings.simplefilter("error", RuntimeWarning)
             yd = blk(xd)
-            (gxd,) = torch.autograd.grad(yd, xd, gy.to(DEV))
+            gxd, *gpd = torch.autograd.grad(yd, [xd, *blk.parameters()], gy.to(DEV))
         assert _native.launch_count() > n0
         P.close(f"{reshape[1]} y", yd, yc)
         P.close(f"{reshape[1]} gx", gxd, gxc)
+        for n, a, b in zip(names, gpd, gpc):            # every parameter gradient of the block, same host reference
+            P.close(f"{reshape[1]} d{n}", a, b)

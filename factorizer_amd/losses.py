@@ -14,6 +14,9 @@ is kept as a separate, documented loss.
 
 Device tensors: one fused reduction pass + one fused gradient pass (csrc/loss.hip); CPU tensors:
 composed ATen ops.
+
+`DeepSupervisionLoss` / `deep_supervision_loss` (MONAI 1.4 semantics, restated below) sum that loss over the head list
+of a ``num_deep_supr`` network; coarse levels read the full-resolution target through an index map (csrc/loss_ds.hip).
 """
 from __future__ import annotations
 
@@ -33,6 +36,32 @@ def dice_bce_loss_composed(logits, target, smooth: float = 1e-5):
     return dice.mean() + F.binary_cross_entropy_with_logits(logits, target)
 
 
+def _bce_finish(part, planes, V, smooth):
+    """(loss, coef (planes, 2) = {2·inter + smooth, den + smooth}) from the partials (planes, nchunk, 4) of a Dice + BCE sums pass"""
+    s = part.sum(dim=1)  # (planes, 4) — tiny
+    num = 2.0 * s[:, 0] + smooth
+    den = s[:, 1] + s[:, 2] + smooth
+    loss = (1.0 - num / den).mean() + s[:, 3].sum() / (planes * V)
+    return loss, torch.stack([num, den], dim=1).contiguous()
+
+
+def _ce_finish(part, B, C, V, smooth):
+    """(loss, coef (B·C, 2)) from the partials (B, nchunk, 3C + 1) of a Dice + CE sums pass"""
+    if B <= 8:   # one finish launch instead of a dozen framework kernels (chunk sum, num, den, means)
+        loss = torch.empty((), dtype=part.dtype, device=part.device)
+        coef = torch.empty((B * C, 2), dtype=part.dtype, device=part.device)
+        with torch.cuda.device(part.device):
+            rc = N.lib().fz_dice_ce_finish(part.data_ptr(), B, C, V, float(smooth), loss.data_ptr(), coef.data_ptr(), N.stream_ptr(part))
+        N.check(rc, "fz_dice_ce_finish")
+        return loss, coef
+    s = part.sum(dim=1)  # (B, 3C+1) — tiny
+    d = s[:, :3 * C].reshape(B, C, 3)
+    num = 2.0 * d[..., 0] + smooth
+    den = d[..., 1] + d[..., 2] + smooth
+    loss = (1.0 - num / den).mean() + s[:, 3 * C].sum() / (B * V)
+    return loss, torch.stack([num, den], dim=-1).reshape(B * C, 2).contiguous()
+
+
 class DiceBCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, smooth):
@@ -47,11 +76,8 @@ class DiceBCEFn(torch.autograd.Function):
             rc = Fn._timed("dice_bce_sums", 8 * z.numel(), lambda: lib.fz_dice_bce_sums(
                 z.data_ptr(), t.data_ptr(), part.data_ptr(), planes, V, N.stream_ptr(z)), cols=z.shape[0] * V)
         N.check(rc, "fz_dice_bce_sums")
-        s = part.sum(dim=1)  # (planes, 4) — tiny
-        num = 2.0 * s[:, 0] + smooth
-        den = s[:, 1] + s[:, 2] + smooth
-        loss = (1.0 - num / den).mean() + s[:, 3].sum() / (planes * V)
-        ctx.save_for_backward(z, t, torch.stack([num, den], dim=1).contiguous())
+        loss, coef = _bce_finish(part, planes, V, smooth)
+        ctx.save_for_backward(z, t, coef)
         ctx.dims = (planes, V)
         return loss
 
@@ -121,19 +147,7 @@ class DiceCEFn(torch.autograd.Function):
             rc = Fn._timed("dice_ce_sums", 8 * z.numel(), lambda: lib.fz_dice_ce_sums(
                 z.data_ptr(), t.data_ptr(), part.data_ptr(), B, C, V, N.stream_ptr(z)), cols=B * V)
         N.check(rc, "fz_dice_ce_sums")
-        if B <= 8:   # one finish launch instead of a dozen framework kernels (chunk sum, num, den, means)
-            loss = torch.empty((), dtype=z.dtype, device=z.device)
-            coef = torch.empty((B * C, 2), dtype=z.dtype, device=z.device)
-            with torch.cuda.device(z.device):
-                rc = lib.fz_dice_ce_finish(part.data_ptr(), B, C, V, float(smooth), loss.data_ptr(), coef.data_ptr(), N.stream_ptr(z))
-            N.check(rc, "fz_dice_ce_finish")
-        else:
-            s = part.sum(dim=1)  # (B, 3C+1) — tiny
-            d = s[:, :3 * C].reshape(B, C, 3)
-            num = 2.0 * d[..., 0] + smooth
-            den = d[..., 1] + d[..., 2] + smooth
-            loss = (1.0 - num / den).mean() + s[:, 3 * C].sum() / (B * V)
-            coef = torch.stack([num, den], dim=-1).reshape(B * C, 2).contiguous()
+        loss, coef = _ce_finish(part, B, C, V, smooth)
         ctx.save_for_backward(z, t, coef)
         ctx.dims = (B, C, V)
         return loss
@@ -180,3 +194,178 @@ class DiceCELoss(torch.nn.Module):
 
     def forward(self, input, target):
         return dice_ce_loss(input, target, self.smooth)
+
+
+# ---- deep supervision: MONAI 1.4 DeepSupervisionLoss over the head list of num_deep_supr networks --------------------
+# ushape.UNet returns one logits tensor per decoder level, finest first.  The loss of the list is Σ_l w_l · loss(z_l, t_l)
+# (not normalised) with t_l the target itself where the level has its extents and its nearest-exact down-sampling otherwise.
+# For an integer ratio r on an axis nearest-exact is the strided pick index = r·i + r//2, which csrc/loss_ds.hip applies as
+# an index map while it reads the full-resolution target: a coarse level then costs the launches of a dense one and writes
+# no target of its own.  (For non-integer ratios torch's float arithmetic and the integer formula floor((2i+1)·S_t/(2·S_l))
+# disagree — 26 -> 11 is the first case — so those are never computed natively.)
+_DS_MODES = ("same", "exp", "two")
+_DS_TKIND = {torch.float32: N.SEG_F32, torch.bfloat16: N.SEG_BF16, torch.uint8: N.SEG_U8, torch.bool: N.SEG_U8}
+
+
+def _ds_check_mode(weight_mode):
+    if weight_mode not in _DS_MODES:
+        raise ValueError(f"deep supervision: weight_mode must be one of {_DS_MODES}, got {weight_mode!r}")
+
+
+def ds_weights(levels: int, weight_mode: str = "exp", weights=None):
+    """the level weights w_0 .. w_{levels-1}: explicit `weights` when there are enough of them, else by `weight_mode`"""
+    _ds_check_mode(weight_mode)
+    if weights is not None and len(weights) >= levels:
+        return [float(w) for w in weights[:levels]]
+    if weight_mode == "same":
+        return [1.0] * levels
+    if weight_mode == "exp":
+        return [max(0.5 ** l, 0.0625) for l in range(levels)]
+    return [1.0 if l == 0 else 0.5 for l in range(levels)]
+
+
+def ds_target_composed(target, size, dtype):
+    """the target of a level of spatial `size` in `dtype`: the target itself at its own size, else nearest-exact"""
+    if tuple(target.shape[2:]) == tuple(size):
+        return target
+    if target.dtype == torch.bool:
+        target = target.view(torch.uint8)
+    return F.interpolate(target, size=tuple(size), mode="nearest-exact").to(dtype)
+
+
+def _lift3(spatial):
+    return (1,) * (3 - len(spatial)) + tuple(int(s) for s in spatial)
+
+
+class DiceCELevelFn(torch.autograd.Function):
+    """DiceCELoss of ONE coarse level against the full-resolution target (csrc/loss_ds.hip).  logits: fp32, contiguous or
+    not; target: as the caller holds it (fp32 / bf16 / uint8 / bool, contiguous) — saved as given, never resampled."""
+
+    @staticmethod
+    def forward(ctx, logits, target, smooth):
+        z = logits.contiguous()
+        t = target.view(torch.uint8) if target.dtype == torch.bool else target
+        B, C = z.shape[:2]
+        geom = (*_lift3(t.shape[2:]), *_lift3(z.shape[2:]), _DS_TKIND[target.dtype])
+        V = z.numel() // (B * C)
+        lib = N.lib()
+        nchunk = lib.fz_dice_bce_chunks(V)
+        tbytes = B * C * V * t.element_size()
+        if C == 1:
+            part = torch.empty((B, nchunk, 4), dtype=z.dtype, device=z.device)
+            with torch.cuda.device(z.device):
+                rc = Fn._timed("dice_bce_ds_sums", 4 * z.numel() + tbytes, lambda: lib.fz_dice_bce_ds_sums(
+                    z.data_ptr(), t.data_ptr(), part.data_ptr(), B, *geom, N.stream_ptr(z)), cols=B * V)
+            N.check(rc, "fz_dice_bce_ds_sums")
+            loss, coef = _bce_finish(part, B, V, smooth)
+        else:
+            part = torch.empty((B, nchunk, 3 * C + 1), dtype=z.dtype, device=z.device)
+            with torch.cuda.device(z.device):
+                rc = Fn._timed("dice_ce_ds_sums", 4 * z.numel() + tbytes, lambda: lib.fz_dice_ce_ds_sums(
+                    z.data_ptr(), t.data_ptr(), part.data_ptr(), B, C, *geom, N.stream_ptr(z)), cols=B * V)
+            N.check(rc, "fz_dice_ce_ds_sums")
+            loss, coef = _ce_finish(part, B, C, V, smooth)
+        ctx.save_for_backward(z, t, coef)
+        ctx.dims = (B, C, V, geom, tbytes)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        z, t, coef = ctx.saved_tensors
+        B, C, V, geom, tbytes = ctx.dims
+        gz = torch.empty_like(z)
+        gs = g.reshape(1).to(z.dtype).contiguous()
+        lib = N.lib()
+        with torch.cuda.device(z.device):
+            if C == 1:
+                rc = Fn._timed("dice_bce_ds_grad", 8 * z.numel() + tbytes, lambda: lib.fz_dice_bce_ds_grad(
+                    z.data_ptr(), t.data_ptr(), coef.data_ptr(), gz.data_ptr(), B, *geom, 1.0 / B, 1.0 / (B * V),
+                    gs.data_ptr(), N.stream_ptr(z)), cols=B * V)
+            else:
+                rc = Fn._timed("dice_ce_ds_grad", 8 * z.numel() + tbytes, lambda: lib.fz_dice_ce_ds_grad(
+                    z.data_ptr(), t.data_ptr(), coef.data_ptr(), gz.data_ptr(), B, C, *geom, 1.0 / (B * C), 1.0 / (B * V),
+                    gs.data_ptr(), N.stream_ptr(z)), cols=B * V)
+        N.check(rc, "fz_dice_bce_ds_grad" if C == 1 else "fz_dice_ce_ds_grad")
+        return gz, None, None
+
+
+def ds_level_launches(B: int, C: int, backward: bool = False) -> int:
+    """native launches of one sampled level: the sums pass, plus fz_dice_ce_finish where DiceCEFn runs it too (C >= 2 and
+    B <= 8; the other finishes are framework reductions of the partials); the backward is one gradient pass"""
+    if backward:
+        return 1
+    return 2 if (C >= 2 and B <= 8) else 1
+
+
+def _ds_level_gate(loss, logits, target):
+    """None when csrc/loss_ds.hip takes this coarse level, else (key, reason) of the composed branch"""
+    if not isinstance(loss, DiceCELoss):
+        return "loss", f"{type(loss).__name__} is not ft.DiceCELoss"
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        return "logits", f"{logits.dtype} logits"
+    B, C = logits.shape[:2]
+    if not 1 <= C <= 8:
+        return "channels", f"C = {C} (native: 1 <= C <= 8)"
+    V = logits.numel() // max(B * C, 1)
+    if V == 0 or V % 4 or V >= 2 ** 31:
+        return "voxels", f"{V} level voxels (native: a multiple of 4 below 2^31)"
+    if len(logits.shape) > 5 or any(st % sl for st, sl in zip(target.shape[2:], logits.shape[2:])):
+        return "ratio", f"target {tuple(target.shape[2:])} over level {tuple(logits.shape[2:])} is not an integer ratio"
+    if target.dtype not in _DS_TKIND or not target.is_contiguous():
+        return "target", f"{target.dtype} target, contiguous = {target.is_contiguous()}"
+    return None
+
+
+def deep_supervision_loss(inputs, target, loss=None, weight_mode: str = "exp", weights=None):
+    """MONAI 1.4 ``DeepSupervisionLoss(loss, weight_mode, weights)(inputs, target)``: Σ_l w_l · loss(inputs[l], target_l) over a
+    list of logits (B, C, *S_l), finest first — what ``Factorizer(..., num_deep_supr=k)`` / ``Deconver(..., num_deep_supr=k)``
+    return.  A tensor, or a list of one tensor whose weight is 1 (every mode gives that), is ``loss(input, target)`` itself.
+    On a device, with ``ft.DiceCELoss``, a coarse level reads the full-resolution target through the nearest-exact index map
+    (csrc/loss_ds.hip); a level the kernels do not take (`_ds_level_gate`) interpolates the target and calls `loss`."""
+    loss = DiceCELoss() if loss is None else loss
+    _ds_check_mode(weight_mode)   # a bad mode is refused whatever the input is
+    if isinstance(inputs, torch.Tensor):
+        if inputs.ndim == target.ndim + 1:
+            raise ValueError(f"deep supervision: the stacked form (B, L, C, *S) {tuple(inputs.shape)} is not supported; "
+                             "pass the list of level logits")
+        return loss(inputs, target)
+    levels = list(inputs)
+    if not levels:
+        raise ValueError("deep supervision: an empty list of logits")
+    w = ds_weights(len(levels), weight_mode, weights)
+    if len(levels) == 1 and w[0] == 1.0:
+        return loss(levels[0], target)
+    total = None
+    for wl, z in zip(w, levels):
+        if z.ndim != target.ndim or z.shape[:2] != target.shape[:2]:
+            raise ValueError(f"deep supervision: logits {tuple(z.shape)} against target {tuple(target.shape)}")
+        if z.shape[2:] == target.shape[2:]:
+            term = loss(z, target)
+        else:
+            why = _ds_level_gate(loss, z, target) if z.is_cuda else ("cpu", "")
+            if why is None:
+                term = DiceCELevelFn.apply(z.float() if z.dtype != torch.float32 else z, target, loss.smooth)
+            else:
+                if z.is_cuda:
+                    from .composed import warn_once
+                    warn_once("deep_supervision_loss:" + why[0], f"no native deep-supervision level for {why[1]}: "
+                              "composed framework ops (interpolate, then the loss)")
+                arith = torch.float32 if z.dtype in (torch.bfloat16, torch.float16) else z.dtype
+                term = loss(z, ds_target_composed(target, z.shape[2:], arith))
+        total = wl * term if total is None else total + wl * term
+    return total
+
+
+class DeepSupervisionLoss(torch.nn.Module):
+    """Drop-in for MONAI 1.4 ``DeepSupervisionLoss(loss, weight_mode="exp", weights=None)`` on the head lists of this package's
+    ``num_deep_supr`` networks (`deep_supervision_loss`)."""
+
+    def __init__(self, loss, weight_mode: str = "exp", weights=None):
+        super().__init__()
+        _ds_check_mode(weight_mode)
+        self.loss = loss
+        self.weight_mode = weight_mode
+        self.weights = None if weights is None else [float(v) for v in weights]
+
+    def forward(self, input, target):
+        return deep_supervision_loss(input, target, self.loss, self.weight_mode, self.weights)

@@ -55,7 +55,7 @@ int fz_version(void);
  * compares fz_abi_version() with the FZ_ABI_VERSION of the header it was written against BEFORE the first call and refuses
  * to run on a mismatch (factorizer_amd/_native.py does).  History: 3 = round 3; 4 = round 4 (`products` / `tune` descriptor
  * fields, `products` argument of fz_conv3_*); 5 = round 5 (the two-window entry points fz_nmf_cf_fwd2 / _bwd2 removed, this
- * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words; fz_gcorr_act / fz_gcorr_wgrad_act / fz_gcorr_mu_bwd: the grouped correlations on bf16 storage) leave it at 7. */
+ * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words; fz_gcorr_act / fz_gcorr_wgrad_act / fz_gcorr_mu_bwd: the grouped correlations on bf16 storage; fz_dice_bce_ds_* / fz_dice_ce_ds_*: the deep-supervision levels of the loss) leave it at 7. */
 #define FZ_ABI_VERSION 7
 int fz_abi_version(void);
 /* Walking order of the fused-core launches (fz_nmf_cf_fwd / fz_nmf_cf_bwd) this THREAD issues from now on: 0 = ascending over
@@ -677,6 +677,23 @@ int fz_dice_ce_sums(const float* z, const float* t, float* part, int B, int C, i
 int fz_dice_ce_finish(const float* part, int B, int C, int64_t V, float smooth, float* loss, float* coef, fz_stream_t stream);
 int fz_dice_ce_grad(const float* z, const float* t, const float* coef, float* gz, int B, int C, int64_t V,
                     float cd, float cb, const float* gscale, fz_stream_t stream);
+
+/* ---- the same four passes for one COARSE level of a deep-supervision head list (MONAI 1.4 DeepSupervisionLoss, restated in
+ * factorizer_amd/losses.py): z (planes | B, C; Ld, Lh, Lw) fp32 at the level's extents, t at the TARGET's extents
+ * (.., Td, Th, Tw) with Tk a multiple of Lk on every axis (1-D / 2-D: leading extents 1), contiguous, of element kind tkind =
+ * FZ_SEG_F32 / FZ_SEG_BF16 / FZ_SEG_U8 (one byte: uint8 or bool).  The level's target value is the nearest-exact pick
+ * t[.., r_z*z + r_z/2, r_y*y + r_y/2, r_x*x + r_x/2], r_k = Tk / Lk, loaded in its own type through 64-bit element offsets
+ * and converted in registers; no down-sampled target exists in memory.  V = Ld*Lh*Lw must be a multiple of 4 below 2^31.
+ * part and coef have the layouts of the dense entry points at that V, so fz_dice_ce_finish (or the caller's own reduction)
+ * serves both; arithmetic per voxel, chunking and summation order are the dense kernels'. */
+int fz_dice_bce_ds_sums(const float* z, const void* t, float* part, int planes, int Td, int Th, int Tw, int Ld, int Lh, int Lw,
+                        int tkind, fz_stream_t stream);
+int fz_dice_bce_ds_grad(const float* z, const void* t, const float* coef, float* gz, int planes, int Td, int Th, int Tw,
+                        int Ld, int Lh, int Lw, int tkind, float cd, float cb, const float* gscale, fz_stream_t stream);
+int fz_dice_ce_ds_sums(const float* z, const void* t, float* part, int B, int C, int Td, int Th, int Tw, int Ld, int Lh, int Lw,
+                       int tkind, fz_stream_t stream);
+int fz_dice_ce_ds_grad(const float* z, const void* t, const float* coef, float* gz, int B, int C, int Td, int Th, int Tw,
+                       int Ld, int Lh, int Lw, int tkind, float cd, float cb, const float* gscale, fz_stream_t stream);
 
 /* ---- sliding-window inference stitching -------------------------------------
  * What MONAI's SlidingWindowInfererAdapt(roi 128^3, sw_batch 2, overlap 0.5, mode "gaussian") does

@@ -372,8 +372,10 @@ def test_outproj_and_mlp_chain_in_one_launch(B, S, bf, C, Hd):
     """Steps 3 + 4 of FactorizerBlock.forward — x1 = x + out_proj(a) (factorizer.py:53,75) and x2 = x1 + mlp(LN(x1))
     (factorizer.py:76; mlp.py:54-63; norm.py:29-34) — as ONE launch (fz_mlp_chain with pre_in: the out-projection on the
     accumulators in front of the chained GEMMs, x1 written once and never read back) against the float64 composition on
-    the CPU and against the two-launch form it replaces.  V = 120 covers a ragged tile, (3, 32·32·40) several tiles per
-    workgroup.  bf16 storage: everything downstream of x1 must see the STORED (rounded) x1, as the two-launch form does.
+    the CPU and against the two-launch form it replaces.  V = 120 covers a ragged tile; (3, 32·32·40) is 480 tiles, below the
+    cap of 512 resident workgroups (240 pairs, below 256, at C = 64): one tile per workgroup (the tile walk:
+    tests/test_gpu_mlp_chain.py).  bf16 storage: everything downstream of x1 must see the STORED (rounded) x1, as the
+    two-launch form does.
     [r5] also at C = 64, hidden 128 (stage 1 of the README model: the 512-thread chain around three pre-split weight images),
     which takes an even number of 256-voxel tiles per sample — V = 384: a ragged second tile; V = 120 is refused."""
     torch.manual_seed(17)
@@ -437,7 +439,8 @@ def test_mlp_chain_backward_with_weight_gradients(B, S, bf, Hd):
     """fz_mlp_chain mode 2 (gemm_chain_bwd_wg_kernel): the input-gradient chain AND dW1, db1, dW2, db2 of the MLP from
     one pass over (g2, z1, x1) — transposed MFMA operands through wave-private LDS, sums carried across the tiles of
     the persistent workgroups, rows added in order.  Against CPU autograd of x + fc2(gelu(fc1(LN(x)))); V = 120
-    covers a ragged tile, (3, 32·32·40) several tiles per workgroup.  Run twice: bit-identical."""
+    covers a ragged tile; (3, 32·32·40) is 480 tiles, one per workgroup (sums carried over several tiles, and the float64
+    reference of the sums: tests/test_gpu_mlp_chain.py).  Run twice: bit-identical."""
     torch.manual_seed(11)
     C = 32    # Hd = 128 (mlp_ratio 4, BraTS bundle): one launch per 64-row half of the hidden tensor
     rnd = (lambda t: t.bfloat16().float()) if bf else (lambda t: t)
@@ -481,7 +484,7 @@ def test_gemm_dw_kernel(B, S, ln, bf):
     """fz_gemm_dw (gemm_dw_kernel): input gradient and weight (+ bias) gradient of a 32 -> 32 layer from one pass —
     out_proj form (y = Wᵀg, gw = Σ g ⊗ a, gb = Σ g) and in_proj form (LayerNorm backward on the accumulators + added
     gradient, gw against the LayerNorm OUTPUT γ x̂ + β, dγ / dβ).  Against CPU autograd; ragged tile (V = 120);
-    several tiles per persistent workgroup; bit-identical when repeated."""
+    at most 480 tiles, one per persistent workgroup (several: tests/test_gpu_mlp_chain.py); bit-identical when repeated."""
     torch.manual_seed(17 + B)
     C = 32
     rnd = (lambda t: t.bfloat16().float()) if bf else (lambda t: t)

@@ -161,7 +161,7 @@ class FactorizerBlock(nn.Module):
                 cfg = dict(geo=f.reshape.geometry, T=mf.num_iters, G=G, solver=sid, nmf_eps=mf.solver.eps,
                            eps1=n1.eps, eps2=n2.eps, core=core is not None)
                 if drop is not None:
-                    cfg["drop"] = drop   # the three sites inside the node (pointwise._block_dropout_fwd)
+                    cfg["drop"] = drop   # the three sites inside the node (pointwise._outproj_mlp_fwd_chain, else _block_tail_fwd)
                 args = (x, n1.weight, n1.bias, f.in_proj.linear.weight, mf.init.u0, mf.init.v0,
                         f.out_proj.linear.weight, f.out_proj.linear.bias, n2.weight, n2.bias,
                         blk[0].linear.weight, blk[0].linear.bias, blk[3].linear.weight, blk[3].linear.bias, cfg)

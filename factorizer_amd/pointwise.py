@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import functools
 import os
 import threading as _threading
 import weakref
@@ -27,13 +28,12 @@ from . import functional as Fn
 
 ACT = {"none": 0, "relu": 1, "gelu": 2}
 LOAD_PLAIN, LOAD_S2D, LOAD_K3, LOAD_S2D_2D, LOAD_K3_2D = 0, 1, 2, 3, 4
-EPI_PLAIN, EPI_D2S, EPI_D2S_2D = 0, 1, 3
+EPI_PLAIN, EPI_D2S, EPI_LNBWD, EPI_D2S_2D = 0, 1, 2, 3
 QL_S2D_2D, QL_K3_2D = LOAD_S2D_2D, LOAD_K3_2D   # fz_wgrad's own names of the two ids (FZ_QL_* in the header): nothing here passes them
 _D2S_FINE = {EPI_D2S: 8, EPI_D2S_2D: 4}   # fine voxels per coarse column of a depth-to-space epilogue
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
+_p = N.ptr   # data_ptr() of a tensor, None of None
 
 
 def _vox(x):
@@ -43,10 +43,17 @@ def _vox(x):
     return v
 
 
+def _ln_stats(B, V, dev):
+    """the (mean, rstd) planes a LayerNorm forward leaves for its backward"""
+    return torch.empty((B, 2, V), dtype=torch.float32, device=dev)
+
+
 # ---- raw launches ---------------------------------------------------------------------------
-def _gemm(xs, w, y, *, B, Cin, Vin, M, K, Ncol, w_t=False, ldw=None, bias=None, ln=None, stats_out=None,
-          bact=0, bmul=None, bmul_kind=0, eact=0, res=None, emul=None, emul_kind=0, src_mode=0, c0=0,
-          loader=LOAD_PLAIN, epilogue=EPI_PLAIN, Di=0, Hi=0, Wi=0, Ho=0, Wo=0, name="gemm", tune=0):
+def _gemm_desc(xs, w, y, *, B, Cin, Vin, M, K, Ncol, w_t=False, ldw=None, bias=None, ln=None, stats_out=None,
+               bact=0, bmul=None, bmul_kind=0, eact=0, res=None, emul=None, emul_kind=0, src_mode=0, c0=0,
+               loader=LOAD_PLAIN, epilogue=EPI_PLAIN, Di=0, Hi=0, Wi=0, Ho=0, Wo=0, name="gemm", tune=0, lnb=None):
+    """(descriptor, timer key, algorithmic bytes, columns, flops) of one GEMM launch.  lnb = (x, stats, γ, gadd or None): the
+    operands of the EPI_LNBWD epilogue (`lnb_part` is the caller's to set: its size comes from fz_gemm_lnbwd_partials)"""
     d = N.GemmDesc()
     d.products = N.products()
     d.tune = tune
@@ -66,11 +73,21 @@ def _gemm(xs, w, y, *, B, Cin, Vin, M, K, Ncol, w_t=False, ldw=None, bias=None, 
     x0 = xs[0]
     d.act_dtype = N.act_dtype(x0)
     nbytes = x0.element_size() * (sum(t.numel() for t in xs) + y.numel() + (res.numel() if res is not None else 0))
-    with torch.cuda.device(x0.device):
-        rc = Fn._timed(f"{name}_{Cin}->{M}", nbytes,
-                       lambda: N.lib().fz_gemm(ctypes.byref(d), N.stream_ptr(x0)),
-                       cols=B * max(Vin, Ncol * _D2S_FINE.get(epilogue, 1)), flops=2 * B * Ncol * M * K)
+    if lnb is not None:
+        d.lnb_x, d.lnb_stats, d.lnb_g, d.lnb_gadd = (_p(t) for t in lnb)
+        nbytes += x0.element_size() * (lnb[0].numel() + (lnb[3].numel() if lnb[3] is not None else 0))
+    return d, f"{name}_{Cin}->{M}", nbytes, B * max(Vin, Ncol * _D2S_FINE.get(epilogue, 1)), 2 * B * Ncol * M * K
+
+
+def _gemm_launch(x0, d, key, nbytes, cols, flops):
+    """fz_gemm of a `_gemm_desc` plan on the current stream of x0's device (the caller holds the device)"""
+    rc = Fn._timed(key, nbytes, lambda: N.lib().fz_gemm(ctypes.byref(d), N.stream_ptr(x0)), cols=cols, flops=flops)
     N.check(rc, "fz_gemm")
+
+
+def _gemm(xs, w, y, **kw):
+    with torch.cuda.device(xs[0].device):
+        _gemm_launch(xs[0], *_gemm_desc(xs, w, y, **kw))
     return y
 
 
@@ -141,6 +158,17 @@ def _ln_backward(gl, x, stats, ln_w, gadd=None):
     return gx, gpar[:C], gpar[C:]
 
 
+def _reduce_affine_rows(part, rows, C, like):
+    """per-workgroup partial rows (rows × 2C: gγ | gβ) of a fused LayerNorm backward -> (gγ, gβ), summed in a fixed order
+    (fz_reduce_rows; the caller holds the device)"""
+    gpar = torch.empty(2 * C, dtype=torch.float32, device=like.device)
+    tmp = torch.empty((64, 2 * C), dtype=torch.float32, device=like.device)
+    with _finish_scope(part, gpar, tmp):
+        rc = N.lib().fz_reduce_rows(part.data_ptr(), rows, 2 * C, gpar.data_ptr(), tmp.data_ptr(), N.stream_ptr(like))
+    N.check(rc, "fz_reduce_rows")
+    return gpar[:C], gpar[C:]
+
+
 def _dgrad_lnbwd(gz, w2, x, stats, ln_w, gadd):
     """gx = LayerNormBackward(W2ᵀ·gz; x, stats, γ) + gadd and (gγ, gβ), in ONE kernel when the
     LayerNorm width is 32, or 64 with a 64-channel gradient (csrc/gemm.hip, mlp_chain64.hip EPI_LNBWD: gl never leaves the accumulators)."""
@@ -153,29 +181,15 @@ def _dgrad_lnbwd(gz, w2, x, stats, ln_w, gadd):
         _gemm([gz], w2, gl, B=B, Cin=Mz, Vin=V, M=C, K=Mz, Ncol=V, w_t=True, ldw=C, name="linear_dgrad")
         return _ln_backward(gl, x, stats, ln_w, gadd=gadd)
     gx = torch.empty_like(x)
-    d = N.GemmDesc()
-    d.products = N.products()
-    d.x[0] = gz.data_ptr()
-    d.nsrc, d.src_mode, d.c0, d.Cin, d.Vin = 1, 0, 0, Mz, V
-    d.w, d.w_t, d.ldw, d.M, d.K = w2.data_ptr(), 1, C, C, Mz
-    d.y, d.Ncol, d.B = gx.data_ptr(), V, B
-    d.loader, d.epilogue = LOAD_PLAIN, 2
-    d.lnb_x, d.lnb_stats, d.lnb_g, d.lnb_gadd = x.data_ptr(), stats.data_ptr(), ln_w.data_ptr(), _p(gadd)
-    d.act_dtype = N.act_dtype(x)
+    d, *timed = _gemm_desc([gz], w2, gx, B=B, Cin=Mz, Vin=V, M=C, K=Mz, Ncol=V, w_t=True, ldw=C, epilogue=EPI_LNBWD,
+                           lnb=(x, stats, ln_w, gadd), name="dgrad_lnbwd")
     rows = N.lib().fz_gemm_lnbwd_partials(ctypes.byref(d))
     part = torch.empty((rows, 2 * C), dtype=torch.float32, device=x.device)
     d.lnb_part = part.data_ptr()
-    gpar = torch.empty(2 * C, dtype=torch.float32, device=x.device)
-    tmp = torch.empty((64, 2 * C), dtype=torch.float32, device=x.device)
-    nbytes = x.element_size() * (gz.numel() + 2 * x.numel() + (gadd.numel() if gadd is not None else 0))
     with torch.cuda.device(x.device):
-        rc = Fn._timed(f"dgrad_lnbwd_{Mz}->{C}", nbytes, lambda: N.lib().fz_gemm(ctypes.byref(d), N.stream_ptr(x)),
-                       cols=B * V, flops=2 * B * V * C * Mz)
-        N.check(rc, "fz_gemm")
-        with _finish_scope(part, gpar, tmp):
-            rc = N.lib().fz_reduce_rows(part.data_ptr(), rows, 2 * C, gpar.data_ptr(), tmp.data_ptr(), N.stream_ptr(x))
-        N.check(rc, "fz_reduce_rows")
-    return gx, gpar[:C], gpar[C:]
+        _gemm_launch(gz, d, *timed)
+        ggamma, gbeta = _reduce_affine_rows(part, rows, C, x)
+    return gx, ggamma, gbeta
 
 
 def _dw_fused_ok(C, V):
@@ -243,6 +257,51 @@ def _mlp_chain_ok(C, Hd, V):
     return os.environ.get("FZ_MLP_CHAIN", "1") != "0" and bool(N.lib().fz_mlp_supported(C, Hd, V))
 
 
+def _mlp_desc(mode, like, w12, w22, *, B, C, Hd, V, inp=None, b1=None, b2=None, ln_w=None, ln_b=None, eps=0.0, stats=None, z1=None,
+              x1=None, out=None):
+    """what every fz_mlp_chain launch fills (mode 0 forward, 1 backward, 2 backward + weight gradients); the mode's own outputs
+    and the pre_* / post_* stages are the caller's to add"""
+    d = N.MlpDesc()
+    d.products = N.products()
+    d.mode, d.inp, d.w1, d.w2, d.b1, d.b2 = mode, _p(inp), w12.data_ptr(), w22.data_ptr(), _p(b1), _p(b2)
+    d.ln_g, d.ln_b, d.ln_eps = _p(ln_w), _p(ln_b), float(eps)
+    d.stats, d.z1, d.x1, d.out = _p(stats), _p(z1), _p(x1), _p(out)
+    d.B, d.C, d.H, d.V = B, C, Hd, V
+    d.act_dtype = N.act_dtype(like)
+    return d
+
+
+def _mlp_chain_fwd(timed, like, ln_w, ln_b, eps, w12, b1, w22, b2, inp=None, pre=None, head=None, drop=None):
+    """The forward chain launch (fz_mlp_chain mode 0) under `timed` = (timer key, algorithmic bytes, flops): x2 = x1 + fc2(gelu(
+    fc1(LN(x1)))) with x1 = `inp`, or — pre = (a, wout2, bout, x) — x1 = x + out_proj(a) formed on the accumulators in front of
+    the chain and written once.  head = (weight (M, C), bias or None): the logits of x2 in the same launch; drop: `_mlp_dropout`.
+    Returns (x1 or None, x2, z1, statistics, logits or None)."""
+    B, C = like.shape[:2]
+    V = _vox(like)
+    Hd = w12.shape[0]
+    new = lambda ch: torch.empty((B, ch, *like.shape[2:]), dtype=like.dtype, device=like.device)  # noqa: E731
+    z1, st, x2 = new(Hd), _ln_stats(B, V, like.device), torch.empty_like(like)
+    d = _mlp_desc(0, like, w12, w22, B=B, C=C, Hd=Hd, V=V, inp=inp, b1=b1, b2=b2, ln_w=ln_w, ln_b=ln_b, eps=eps, stats=st, z1=z1, out=x2)
+    x1 = logits = None
+    if pre is not None:
+        a, wout2, bout, x = pre
+        x1 = torch.empty_like(like)
+        d.pre_in, d.pre_w, d.pre_b, d.pre_res, d.pre_out = a.data_ptr(), wout2.data_ptr(), _p(bout), x.data_ptr(), x1.data_ptr()
+    if head is not None:
+        hw, hb = head
+        logits = new(hw.shape[0])
+        d.post_w, d.post_b, d.post_out, d.post_m = hw.data_ptr(), _p(hb), logits.data_ptr(), hw.shape[0]
+    dd = _mlp_dropout(drop) if drop is not None else None   # block dropout: the three sites inside this launch
+    key, nbytes, flops = timed
+    with torch.cuda.device(like.device):
+        rc = Fn._timed(key, nbytes,
+                       lambda: (N.lib().fz_mlp_chain(ctypes.byref(d), N.stream_ptr(like)) if dd is None
+                                else N.lib().fz_mlp_chain_drop(ctypes.byref(d), ctypes.byref(dd), N.stream_ptr(like))),
+                       cols=B * V, flops=flops)
+    N.check(rc, "fz_mlp_chain")
+    return x1, x2, z1, st, logits
+
+
 def _mlp_fwd_chain(x1, ln_w, ln_b, eps, w12, b1, w22, b2):
     """x2 = x1 + fc2(gelu(fc1(LN(x1)))) in ONE kernel (csrc/mlp_chain32.hip gemm_chain_kernel): the hidden
     tensor goes from the accumulators of the first GEMM into the second; z1 (pre-activation) and
@@ -250,20 +309,8 @@ def _mlp_fwd_chain(x1, ln_w, ln_b, eps, w12, b1, w22, b2):
     B, C = x1.shape[:2]
     V = _vox(x1)
     Hd = w12.shape[0]
-    z1 = torch.empty((B, Hd, *x1.shape[2:]), dtype=x1.dtype, device=x1.device)
-    st = torch.empty((B, 2, V), dtype=torch.float32, device=x1.device)
-    x2 = torch.empty_like(x1)
-    d = N.MlpDesc()
-    d.products = N.products()
-    d.mode, d.inp, d.w1, d.w2, d.b1, d.b2 = 0, x1.data_ptr(), w12.data_ptr(), w22.data_ptr(), _p(b1), _p(b2)
-    d.ln_g, d.ln_b, d.ln_eps = ln_w.data_ptr(), ln_b.data_ptr(), float(eps)
-    d.stats, d.z1, d.out = st.data_ptr(), z1.data_ptr(), x2.data_ptr()
-    d.B, d.C, d.H, d.V = B, C, Hd, V
-    d.act_dtype = N.act_dtype(x1)
-    with torch.cuda.device(x1.device):
-        rc = Fn._timed(f"mlp_chain_fwd_{C}", x1.element_size() * (2 * x1.numel() + z1.numel()),
-                       lambda: N.lib().fz_mlp_chain(ctypes.byref(d), N.stream_ptr(x1)), cols=B * V, flops=4 * B * V * C * Hd)
-    N.check(rc, "fz_mlp_chain")
+    timed = (f"mlp_chain_fwd_{C}", x1.element_size() * (2 * x1.numel() + B * Hd * V), 4 * B * V * C * Hd)
+    _, x2, z1, st, _ = _mlp_chain_fwd(timed, x1, ln_w, ln_b, eps, w12, b1, w22, b2, inp=x1)
     return x2, z1, st
 
 
@@ -282,31 +329,9 @@ def _outproj_mlp_fwd_chain(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2,
     B, C = a.shape[:2]
     V = _vox(a)
     Hd = w12.shape[0]
-    z1 = torch.empty((B, Hd, *a.shape[2:]), dtype=a.dtype, device=a.device)
-    st = torch.empty((B, 2, V), dtype=torch.float32, device=a.device)
-    x1 = torch.empty_like(a)
-    x2 = torch.empty_like(a)
-    d = N.MlpDesc()
-    d.products = N.products()
-    d.mode, d.inp, d.w1, d.w2, d.b1, d.b2 = 0, None, w12.data_ptr(), w22.data_ptr(), _p(b1), _p(b2)
-    d.ln_g, d.ln_b, d.ln_eps = ln_w.data_ptr(), ln_b.data_ptr(), float(eps)
-    d.stats, d.z1, d.out = st.data_ptr(), z1.data_ptr(), x2.data_ptr()
-    d.B, d.C, d.H, d.V = B, C, Hd, V
-    d.act_dtype = N.act_dtype(a)
-    d.pre_in, d.pre_w, d.pre_b, d.pre_res, d.pre_out = a.data_ptr(), wout2.data_ptr(), _p(bout), x.data_ptr(), x1.data_ptr()
-    dd = _mlp_dropout(drop) if drop is not None else None   # block dropout: the three sites inside this launch
-    logits = None
-    if head is not None:
-        hw, hb = head
-        Mh = hw.shape[0]
-        logits = torch.empty((B, Mh, *a.shape[2:]), dtype=a.dtype, device=a.device)
-        d.post_w, d.post_b, d.post_out, d.post_m = hw.data_ptr(), _p(hb), logits.data_ptr(), Mh
-    with torch.cuda.device(a.device):
-        rc = Fn._timed(f"outproj_mlp_chain_fwd_{C}", a.element_size() * (4 * a.numel() + z1.numel() + (logits.numel() if head is not None else 0)),
-                       lambda: (N.lib().fz_mlp_chain(ctypes.byref(d), N.stream_ptr(a)) if dd is None
-                                else N.lib().fz_mlp_chain_drop(ctypes.byref(d), ctypes.byref(dd), N.stream_ptr(a))),
-                       cols=B * V, flops=4 * B * V * C * Hd + 2 * B * V * C * C)
-    N.check(rc, "fz_mlp_chain")
+    nlogits = B * head[0].shape[0] * V if head is not None else 0
+    timed = (f"outproj_mlp_chain_fwd_{C}", a.element_size() * (4 * a.numel() + B * Hd * V + nlogits), 4 * B * V * C * Hd + 2 * B * V * C * C)
+    x1, x2, z1, st, logits = _mlp_chain_fwd(timed, a, ln_w, ln_b, eps, w12, b1, w22, b2, pre=(a, wout2, bout, x), head=head, drop=drop)
     if head is not None:
         return x1, x2, z1, st, logits
     return x1, x2, z1, st
@@ -321,23 +346,14 @@ def _mlp_bwd_chain(g2, z1, w12, w22, x1, st, ln_w):
     gx1 = torch.empty_like(x1)
     rows = N.lib().fz_mlp_partials(B, V)
     part = torch.empty((rows, 2 * C), dtype=torch.float32, device=x1.device)
-    gpar = torch.empty(2 * C, dtype=torch.float32, device=x1.device)
-    tmp = torch.empty((64, 2 * C), dtype=torch.float32, device=x1.device)
-    d = N.MlpDesc()
-    d.products = N.products()
-    d.mode, d.inp, d.w1, d.w2 = 1, g2.data_ptr(), w12.data_ptr(), w22.data_ptr()
-    d.ln_g, d.stats, d.z1, d.gz1, d.x1 = ln_w.data_ptr(), st.data_ptr(), z1.data_ptr(), gz1.data_ptr(), x1.data_ptr()
-    d.out, d.part = gx1.data_ptr(), part.data_ptr()
-    d.B, d.C, d.H, d.V = B, C, Hd, V
-    d.act_dtype = N.act_dtype(x1)
+    d = _mlp_desc(1, x1, w12, w22, B=B, C=C, Hd=Hd, V=V, inp=g2, ln_w=ln_w, stats=st, z1=z1, x1=x1, out=gx1)
+    d.gz1, d.part = gz1.data_ptr(), part.data_ptr()
     with torch.cuda.device(x1.device):
         rc = Fn._timed(f"mlp_chain_bwd_{C}", x1.element_size() * (3 * x1.numel() + 2 * z1.numel()),
                        lambda: N.lib().fz_mlp_chain(ctypes.byref(d), N.stream_ptr(x1)), cols=B * V, flops=4 * B * V * C * Hd)
         N.check(rc, "fz_mlp_chain")
-        with _finish_scope(part, gpar, tmp):
-            rc = N.lib().fz_reduce_rows(part.data_ptr(), rows, 2 * C, gpar.data_ptr(), tmp.data_ptr(), N.stream_ptr(x1))
-        N.check(rc, "fz_reduce_rows")
-    return gz1, gx1, gpar[:C], gpar[C:]
+        ggamma, gbeta = _reduce_affine_rows(part, rows, C, x1)
+    return gz1, gx1, ggamma, gbeta
 
 
 def _mlp_wgrad_fused_ok(C, Hd, V):
@@ -359,16 +375,10 @@ def _mlp_bwd_chain_wgrad(g2, z1, w12, w22, x1, st, ln_w, ln_b):
     gw2 = _GB.out_like(w22, (C, Hd), torch.float32)
     gb1 = torch.empty(Hd, dtype=torch.float32, device=dev)
     gb2 = torch.empty(C, dtype=torch.float32, device=dev)
-    d = N.MlpDesc()
-    d.products = N.products()
-    d.mode, d.inp, d.w1, d.w2 = 2, g2.data_ptr(), w12.data_ptr(), w22.data_ptr()
-    d.ln_g, d.ln_b, d.stats, d.z1, d.x1 = ln_w.data_ptr(), ln_b.data_ptr(), st.data_ptr(), z1.data_ptr(), x1.data_ptr()
-    d.out, d.gln, d.wpart = gx1.data_ptr(), gpar.data_ptr(), wpart.data_ptr()
-    d.gw1, d.gb1, d.gw2, d.gb2 = gw1.data_ptr(), gb1.data_ptr(), gw2.data_ptr(), gb2.data_ptr()
     glp = torch.empty(x1.shape, dtype=torch.float32, device=dev) if Hd == 128 else None
-    d.glp = _p(glp)
-    d.B, d.C, d.H, d.V = B, C, Hd, V
-    d.act_dtype = N.act_dtype(x1)
+    d = _mlp_desc(2, x1, w12, w22, B=B, C=C, Hd=Hd, V=V, inp=g2, ln_w=ln_w, ln_b=ln_b, stats=st, z1=z1, x1=x1, out=gx1)
+    d.gln, d.wpart, d.glp = gpar.data_ptr(), wpart.data_ptr(), _p(glp)
+    d.gw1, d.gb1, d.gw2, d.gb2 = gw1.data_ptr(), gb1.data_ptr(), gw2.data_ptr(), gb2.data_ptr()
     # algorithmic bytes: H = 64: g2, z1, x1 in, gx1 out; H = 128: both halves read g2 and x1, + the fp32 partial out and in
     nbytes = x1.element_size() * (3 * x1.numel() + z1.numel()) + (0 if Hd == 64 else x1.element_size() * 2 * x1.numel() + 8 * x1.numel())
     with torch.cuda.device(dev), _finish_scope(wpart, gpar, gw1, gb1, gw2, gb2):
@@ -609,7 +619,6 @@ def _fwd(fn):
     TENSOR argument of `apply` — a float, a string, a dict, a tuple or a None takes none — so `_param_sinks_ok` must not index
     `next_functions` with the argument position.  (The outermost forward of a node sets the map: LinearFn and SkipConvK2S2Fn
     hand their ctx on to another Function's forward.)"""
-    import functools
     inner = N.capture_products(fn)
 
     @functools.wraps(fn)
@@ -692,7 +701,6 @@ def _param_sinks_ok(ctx) -> bool:
 
 def _bwd(fn):
     """decorator of every backward below: N.with_products + the deferral decision above (made once per node)"""
-    import functools
     inner = N.with_products(fn)
 
     @functools.wraps(fn)
@@ -738,6 +746,25 @@ def _head_rows_reduce(part, rows, w2, M, like):
     return gw, gb
 
 
+def _head_bwd(gy, z, w2):
+    """(gz, gw, gb) of the head Linear(32 -> M <= 4), y = w2 z + b: input, weight and bias gradient in one bandwidth-bound pass
+    (csrc/headbwd.hip)"""
+    B, C = z.shape[:2]
+    V = _vox(z)
+    M = w2.shape[0]
+    lib = N.lib()
+    gz = torch.empty_like(z)
+    rows = lib.fz_head_bwd_rows()
+    part = torch.empty(lib.fz_head_bwd_workspace_bytes() // 4, dtype=torch.float32, device=z.device)
+    with torch.cuda.device(z.device):
+        rc = Fn._timed(f"head_bwd_{C}->{M}", z.element_size() * (gy.numel() + 2 * z.numel()),
+                       lambda: lib.fz_head_bwd(gy.data_ptr(), z.data_ptr(), w2.data_ptr(), gz.data_ptr(), part.data_ptr(),
+                                               B, M, C, V, N.act_dtype(z), N.stream_ptr(z)), cols=B * V)
+        N.check(rc, "fz_head_bwd")
+        gw, gb = _head_rows_reduce(part, rows, w2, M, z)
+    return gz, gw, gb
+
+
 # ---- LayerNorm → Linear → [ReLU] -----------------------------------------------------------
 class LNLinearFn(torch.autograd.Function):
     @staticmethod
@@ -749,7 +776,7 @@ class LNLinearFn(torch.autograd.Function):
         M = w.shape[0]
         w2 = w.reshape(M, C)
         y = torch.empty((B, M, *x.shape[2:]), dtype=x.dtype, device=x.device)
-        stats = torch.empty((B, 2, V), dtype=torch.float32, device=x.device)
+        stats = _ln_stats(B, V, x.device)
         _gemm([x], w2, y, B=B, Cin=C, Vin=V, M=M, K=C, Ncol=V, bias=b, ln=(ln_w, ln_b, eps), stats_out=stats,
               eact=ACT["relu" if act == "relu_out" else act], name="ln_linear")
         ctx.save_for_backward(x, stats, ln_w, ln_b, w2, y if act == "relu" else None)
@@ -807,20 +834,10 @@ class ActLinearResFn(torch.autograd.Function):
         B, C = z.shape[:2]
         V = _vox(z)
         M = w2.shape[0]
-        gz = torch.empty_like(z)
         if M <= 4 and C == 32 and ctx.bact == "none" and V % 4 == 0 and _HEAD_BWD:
-            # the head (32 -> out_channels): input, weight and bias gradient in one bandwidth-bound pass (csrc/headbwd.hip)
-            lib = N.lib()
-            rows = lib.fz_head_bwd_rows()
-            part = torch.empty(lib.fz_head_bwd_workspace_bytes() // 4, dtype=torch.float32, device=z.device)
-            es = z.element_size()
-            with torch.cuda.device(z.device):
-                rc = Fn._timed(f"head_bwd_{C}->{M}", es * (gy.numel() + 2 * z.numel()),
-                               lambda: lib.fz_head_bwd(gy.data_ptr(), z.data_ptr(), w2.data_ptr(), gz.data_ptr(), part.data_ptr(),
-                                                       B, M, C, V, N.act_dtype(z), N.stream_ptr(z)), cols=B * V)
-                N.check(rc, "fz_head_bwd")
-                gw, gb = _head_rows_reduce(part, rows, w2, M, z)
+            gz, gw, gb = _head_bwd(gy, z, w2)   # the head (32 -> out_channels)
             return gz, gw.reshape(ctx.wshape), (gb if ctx.has_bias else None), (gy if ctx.has_res else None), None
+        gz = torch.empty_like(z)
         _gemm([gy], w2, gz, B=B, Cin=M, Vin=V, M=C, K=M, Ncol=V, w_t=True, ldw=C,
               emul=(z if ctx.bact != "none" else None), emul_kind=ACT[ctx.bact], name="linear_dgrad")
         gw = _GB.out_like(w2)
@@ -896,7 +913,7 @@ class LayerNormFn(torch.autograd.Function):
         B, C = x.shape[:2]
         V = _vox(x)
         y = torch.empty_like(x)
-        stats = torch.empty((B, 2, V), dtype=torch.float32, device=x.device)
+        stats = _ln_stats(B, V, x.device)
         with torch.cuda.device(x.device):
             rc = Fn._timed(f"ln_fwd_{C}", 2 * x.element_size() * x.numel(), lambda: N.lib().fz_ln_fwd(
                 x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), stats.data_ptr(), B, C, V, eps,
@@ -1417,7 +1434,7 @@ def cat_linear(x1, x2, w, b=None):
     return linear_cf(torch.cat([x1, x2], dim=1), w, b)
 
 
-# ---- dropout route of the block (training mode, 0 < p < 1 at some site; csrc/dropout.hip) -----------------------------------
+# ---- launches of the block outside the chain kernels; its dropout sites (training mode, 0 < p < 1 at some site; csrc/dropout.hip) ----
 def _block_dropout_bits(x, C, Hd, drop):
     """(bits0, bits1, bits2): the keep-bit planes of the three sites (None where p = 0), from ONE seed drawn here — the block
     forward's first use of the device generator (functional.dropout_seed)."""
@@ -1426,15 +1443,15 @@ def _block_dropout_bits(x, C, Hd, drop):
     return tuple(None if p == 0 else Fn.dropout_keep_bits(seed, s, B, ch, V, p) for s, (ch, p) in enumerate(zip((C, Hd, C), drop)))
 
 
-def _block_dropout_fwd(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2, drop, bits):
-    """steps 3 + 4 of the block with the dropout sites (x1, x2, z1, LayerNorm-2 statistics):
-    x1 = x + M0 s0 (Wo a + bo);  z1 = W1 LN2(x1) + b1;  x2 = x1 + M2 s2 (W2 M1 s1 gelu(z1) + b2).  A site with p = 0 is the
-    plain layer (the residual add and the GELU stay in the GEMM epilogue / operand load)."""
+def _block_tail_fwd(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2, drop=None, bits=(None, None, None)):
+    """steps 3 + 4 of the block, one launch per layer, each of the three dropout sites optional (x1, x2, z1, LayerNorm-2 statistics):
+    x1 = x + M0 s0 (Wo a + bo);  z1 = W1 LN2(x1) + b1;  x2 = x1 + M2 s2 (W2 M1 s1 gelu(z1) + b2).  A site that is not live (p = 0, or
+    no dropout at all) is the plain layer: the residual add and the GELU stay in the GEMM epilogue / operand load."""
     B, C = x.shape[:2]
     V = _vox(x)
     Hd = w12.shape[0]
     new = lambda ch: torch.empty((B, ch, *x.shape[2:]), dtype=x.dtype, device=x.device)  # noqa: E731
-    (p0, p1, p2), (m0, m1, m2) = drop, bits
+    (p0, p1, p2), (m0, m1, m2) = drop or (0, 0, 0), bits
     if m0 is not None:
         o = new(C)
         _gemm([a], wout2, o, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, bias=bout, name="linear")
@@ -1444,7 +1461,7 @@ def _block_dropout_fwd(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2, dro
         x1 = new(C)
         _gemm([a], wout2, x1, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, bias=bout, res=x, name="act_linear_res")
     z1 = new(Hd)
-    st2 = torch.empty((B, 2, V), dtype=torch.float32, device=x.device)
+    st2 = _ln_stats(B, V, x.device)
     _gemm([x1], w12, z1, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, bias=b1, ln=(ln_w, ln_b, eps), stats_out=st2, name="ln_linear")
     h, bact = (Fn.dropout_apply(N.DROP_GELU, m1, p1, z1), ACT["none"]) if m1 is not None else (z1, ACT["gelu"])
     if m2 is not None:
@@ -1496,7 +1513,7 @@ class FactorizerBlockFn(torch.autograd.Function):
             t, st1 = t_pre, st_pre
         else:
             t = new(C)
-            st1 = torch.empty((B, 2, V), dtype=torch.float32, device=x.device)
+            st1 = _ln_stats(B, V, x.device)
             _gemm([x], win2, t, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, ln=(n1w, n1b, cfg["eps1"]), stats_out=st1,
                   eact=ACT["relu"], name="ln_linear")
         # 2. a = inverse(NMF(matricize(t)))
@@ -1510,31 +1527,18 @@ class FactorizerBlockFn(torch.autograd.Function):
             del ym
         # 3. x1 = x + out_proj(a)   4. z1 = fc1(LN2(x1)) ; x2 = x1 + fc2(gelu(z1))
         logits = None
-        fused_drop = drop is not None and _mlp_drop_ok(C, Hd, V) and a.is_contiguous()
-        if fused_drop:
-            # the README block: the three masks are read inside the out-projection + MLP chain launch
-            x1, x2, z1, st2 = _outproj_mlp_fwd_chain(a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2, drop=(bits, drop))
-        elif drop is not None:
-            x1, x2, z1, st2 = _block_dropout_fwd(a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2, drop, bits)
-        elif _outproj_mlp_ok(C, Hd, V) and a.is_contiguous() and x.is_contiguous():
-            if head_w is not None:
-                x1, x2, z1, st2, logits = _outproj_mlp_fwd_chain(a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2,
-                                                                 head=(head_w.reshape(head_w.shape[0], C), head_b))
-            else:
-                x1, x2, z1, st2 = _outproj_mlp_fwd_chain(a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2)   # both in one launch
-        else:
+        tail = (a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2)
+        if (_mlp_drop_ok if drop is not None else _outproj_mlp_ok)(C, Hd, V) and a.is_contiguous():
+            # both in one launch; the README block's three masks are read inside it, else the head, when asked, is applied to x2 in it
+            head = (head_w.reshape(head_w.shape[0], C), head_b) if head_w is not None and drop is None else None
+            x1, x2, z1, st2, *logits = _outproj_mlp_fwd_chain(*tail, head=head, drop=(bits, drop) if drop is not None else None)
+            logits = logits[0] if logits else None
+        elif drop is None and _mlp_chain_ok(C, Hd, V):
             x1 = new(C)
             _gemm([a], wout2, x1, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, bias=bout, res=x, name="act_linear_res")
-            if _mlp_chain_ok(C, Hd, V):
-                x2, z1, st2 = _mlp_fwd_chain(x1, n2w, n2b, cfg["eps2"], w12, b1, w22, b2)
-            else:
-                z1 = new(Hd)
-                st2 = torch.empty((B, 2, V), dtype=torch.float32, device=x.device)
-                _gemm([x1], w12, z1, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, bias=b1, ln=(n2w, n2b, cfg["eps2"]),
-                      stats_out=st2, name="ln_linear")
-                x2 = new(C)
-                _gemm([z1], w22, x2, B=B, Cin=Hd, Vin=V, M=C, K=Hd, Ncol=V, bias=b2, bact=ACT["gelu"], res=x1,
-                      name="act_linear_res")
+            x2, z1, st2 = _mlp_fwd_chain(x1, n2w, n2b, cfg["eps2"], w12, b1, w22, b2)
+        else:
+            x1, x2, z1, st2 = _block_tail_fwd(*tail, drop, bits)
         ctx.save_for_backward(x, st1, t, a, x1, st2, z1, m, n1w, n1b, win2, u0c, v0c, wout2, n2w, n2b, w12, w22, *bits)
         ctx.cfg = cfg
         ctx.shapes = (win.shape, wout.shape, w1.shape, w2.shape)
@@ -1581,65 +1585,46 @@ class FactorizerBlockFn(torch.autograd.Function):
                 return _wgrad(*args, **kw)
 
         # --- MLP ---
-        chain = _mlp_chain_ok(C, Hd, V)
-        go_drop = None
-        if drop is not None:
-            # g_f = M2 s2 g2 feeds fc2's gradients; gz1 = M1 s1 (W2ᵀ g_f) gelu'(z1); dW2 = g_f hᵀ with h = M1 s1 gelu(z1) formed
-            # again from z1 and the saved bits; the residual path of the MLP keeps g2 itself
-            (p0, p1, p2), (m0, m1, m2) = drop, bits
-            gf = Fn.dropout_apply(N.DROP_RES, m2, p2, g2) if m2 is not None else g2
-            gw2 = _GB.out_like(w22)
-            gb2 = torch.empty(C, dtype=torch.float32, device=dev)
-            if m1 is not None:
-                gh = torch.empty_like(z1)
-                _gemm([gf], w22, gh, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, w_t=True, ldw=Hd, name="linear_dgrad")
-                gz1 = Fn.dropout_apply(N.DROP_GELU_BWD, m1, p1, gh, z1)
-                del gh
-                h = Fn.dropout_apply(N.DROP_GELU, m1, p1, z1)
-                wgrad(gf, [h], gw2, B=B, M=C, Cin=Hd, K=Hd, Vq=V, Ncols=V, gbias=gb2, name="wgrad_linear")
-                del h
-            else:
-                gz1 = torch.empty_like(z1)
-                _gemm([gf], w22, gz1, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, w_t=True, ldw=Hd, emul=z1,
-                      emul_kind=ACT["gelu"], name="linear_dgrad")
-                wgrad(gf, [z1], gw2, B=B, M=C, Cin=Hd, K=Hd, Vq=V, Ncols=V, gbias=gb2, qact=ACT["gelu"], name="wgrad_linear")
-            del gf
-            gx1, gg2, gbt2 = _dgrad_lnbwd(gz1, w12, x1, st2, n2w, g2)
-            gw1 = _GB.out_like(w12)
-            gb1 = torch.empty(Hd, dtype=torch.float32, device=dev)
-            wgrad(gz1, [x1], gw1, B=B, M=Hd, Cin=C, K=C, Vq=V, Ncols=V, gbias=gb1, stats=st2, ln=(n2w, n2b),
-                  name="wgrad_ln_linear")
-            del gz1
-            # out_proj sees g_o = M0 s0 gx1 (fz_gemm_dw applies it where it reads g, else one pass here); the LayerNorm-1
-            # backward below adds the unmasked gx1 (the residual path)
-            go = gx1
-            if m0 is not None:
-                if _dw_fused_ok(C, V):
-                    go_drop = (m0, p0)
-                else:
-                    go = Fn.dropout_apply(N.DROP_RES, m0, p0, gx1)
-        elif _mlp_wgrad_fused_ok(C, Hd, V):
+        chain = _mlp_chain_ok(C, Hd, V) and drop is None
+        (p0, p1, p2), (m0, m1, m2) = drop or (0, 0, 0), bits
+        if drop is None and _mlp_wgrad_fused_ok(C, Hd, V):
             # input-gradient chain + both weight gradients in one pass over (g2, z1, x1)
             gx1, gg2, gbt2, gw1, gb1, gw2, gb2 = _mlp_bwd_chain_wgrad(g2, z1, w12, w22, x1, st2, n2w, n2b)
         else:
+            # One sequence, each mask optional: g_f = M2 s2 g2 feeds fc2's gradients; gz1 = M1 s1 (W2ᵀ g_f) gelu'(z1); dW2 = g_f hᵀ with
+            # h = M1 s1 gelu(z1) formed again from z1 and the saved bits; the residual path of the MLP keeps g2 itself.  A site
+            # that is not live leaves its factor in the GEMM epilogue / operand load (site 1: the GELU and its derivative); without
+            # dropout the chain kernel, where it fits, forms gz1 and gx1 in one launch.
+            gelu = ACT["gelu" if m1 is None else "none"]
+            gf = Fn.dropout_apply(N.DROP_RES, m2, p2, g2) if m2 is not None else g2
+            gw2 = _GB.out_like(w22)
+            gb2 = torch.empty(C, dtype=torch.float32, device=dev)
             if chain:
                 gz1, gx1, gg2, gbt2 = _mlp_bwd_chain(g2, z1, w12, w22, x1, st2, n2w)   # + residual path of the MLP
             else:
                 gz1 = torch.empty_like(z1)
-                _gemm([g2], w22, gz1, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, w_t=True, ldw=Hd, emul=z1,
-                      emul_kind=ACT["gelu"], name="linear_dgrad")
-            gw2 = _GB.out_like(w22)
-            gb2 = torch.empty(C, dtype=torch.float32, device=dev)
-            wgrad(g2, [z1], gw2, B=B, M=C, Cin=Hd, K=Hd, Vq=V, Ncols=V, gbias=gb2, qact=ACT["gelu"], name="wgrad_linear")
+                _gemm([gf], w22, gz1, B=B, Cin=C, Vin=V, M=Hd, K=C, Ncol=V, w_t=True, ldw=Hd, emul=(z1 if m1 is None else None),
+                      emul_kind=gelu, name="linear_dgrad")
+                if m1 is not None:
+                    gz1 = Fn.dropout_apply(N.DROP_GELU_BWD, m1, p1, gz1, z1)
+            h = Fn.dropout_apply(N.DROP_GELU, m1, p1, z1) if m1 is not None else z1
+            wgrad(gf, [h], gw2, B=B, M=C, Cin=Hd, K=Hd, Vq=V, Ncols=V, gbias=gb2, qact=gelu, name="wgrad_linear")
+            del h, gf
             if not chain:
                 gx1, gg2, gbt2 = _dgrad_lnbwd(gz1, w12, x1, st2, n2w, g2)      # + residual path of the MLP
             gw1 = _GB.out_like(w12)
             gb1 = torch.empty(Hd, dtype=torch.float32, device=dev)
             wgrad(gz1, [x1], gw1, B=B, M=Hd, Cin=C, K=C, Vq=V, Ncols=V, gbias=gb1, stats=st2, ln=(n2w, n2b),
-                   name="wgrad_ln_linear")
+                  name="wgrad_ln_linear")
             del gz1
-        if drop is None:
-            go = gx1
+        # out_proj sees g_o = M0 s0 gx1 (fz_gemm_dw applies it where it reads g, else one pass here); the LayerNorm-1
+        # backward below adds the unmasked gx1 (the residual path)
+        go, go_drop = gx1, None
+        if m0 is not None:
+            if _dw_fused_ok(C, V):
+                go_drop = (m0, p0)
+            else:
+                go = Fn.dropout_apply(N.DROP_RES, m0, p0, gx1)
         # --- out_proj ---
         dw = _dw_fused_ok(C, V)
         if dw:
@@ -1757,17 +1742,7 @@ class HeadOfBlockFn(torch.autograd.Function):
         gl = gl.contiguous()
         if gl.dtype != y.dtype:
             gl = gl.to(y.dtype)
-        gy = torch.empty_like(y)
-        lib = N.lib()
-        rows = lib.fz_head_bwd_rows()
-        part = torch.empty(lib.fz_head_bwd_workspace_bytes() // 4, dtype=torch.float32, device=y.device)
-        es = y.element_size()
-        with torch.cuda.device(y.device):
-            rc = Fn._timed(f"head_bwd_{C}->{M}", es * (gl.numel() + 2 * y.numel()),
-                           lambda: lib.fz_head_bwd(gl.data_ptr(), y.data_ptr(), w2.data_ptr(), gy.data_ptr(), part.data_ptr(),
-                                                   B, M, C, V, N.act_dtype(y), N.stream_ptr(y)), cols=B * V)
-            N.check(rc, "fz_head_bwd")
-            gw, gb = _head_rows_reduce(part, rows, w2, M, y)
+        gy, gw, gb = _head_bwd(gl, y, w2)
         return gy, gw.reshape(ctx.wshape), (gb if ctx.has_bias else None), None
 
 

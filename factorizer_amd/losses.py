@@ -12,11 +12,12 @@ evaluation is restated:
 `dice_bce_loss` (sigmoid Dice + per-channel BCE for any C) is NOT the recipe's objective for C > 1; it
 is kept as a separate, documented loss.
 
-Device tensors: one fused reduction pass + one fused gradient pass (csrc/loss.hip); CPU tensors:
-composed ATen ops.
+Device tensors: one fused reduction pass + one fused gradient pass (csrc/loss.hip) behind ONE autograd Function,
+`DiceLossFn`, whatever the kind (Dice + BCE, Dice + CE) and the way the target is read; CPU tensors: composed ATen ops.
 
 `DeepSupervisionLoss` / `deep_supervision_loss` (MONAI 1.4 semantics, restated below) sum that loss over the head list
-of a ``num_deep_supr`` network; coarse levels read the full-resolution target through an index map (csrc/loss_ds.hip).
+of a ``num_deep_supr`` network; coarse levels read the full-resolution target through an index map (the same kernels with
+their level reader).
 """
 from __future__ import annotations
 
@@ -62,37 +63,72 @@ def _ce_finish(part, B, C, V, smooth):
     return loss, torch.stack([num, den], dim=-1).reshape(B * C, 2).contiguous()
 
 
-class DiceBCEFn(torch.autograd.Function):
+_DS_TKIND = {torch.float32: N.SEG_F32, torch.bfloat16: N.SEG_BF16, torch.uint8: N.SEG_U8, torch.bool: N.SEG_U8}
+
+
+def _lift3(spatial):
+    return (1,) * (3 - len(spatial)) + tuple(int(s) for s in spatial)
+
+
+class DiceLossFn(torch.autograd.Function):
+    """The native loss of every path: one sums pass and a finish forward, one gradient pass backward — the entry points
+    fz_dice_{bce,ce}[_ds]_{sums,grad} of csrc/loss.hip, timed under their names without the fz_.
+    kind: "bce" — every (b, c) plane on its own, partials (B·C, nchunk, 4), `_bce_finish` — or "ce" — the C channels of a
+    batch item together, partials (B, nchunk, 3C + 1), `_ce_finish`.
+    level: False — the target is fp32 at the logits' extents — or True — ONE coarse deep-supervision level against the
+    full-resolution target as the caller holds it (fp32 / bf16 / uint8 / bool, contiguous): saved as given, never resampled,
+    read through the index map (the fz_dice_*_ds_* entry points).  logits: fp32, contiguous or not."""
+
     @staticmethod
-    def forward(ctx, logits, target, smooth):
+    def forward(ctx, logits, target, smooth, kind, level):
         z = logits.contiguous()
-        t = target.contiguous()
-        planes = z.shape[0] * z.shape[1]
-        V = z.numel() // planes
+        B, C = z.shape[:2]
+        V = z.numel() // (B * C)
+        if level:
+            t = target.view(torch.uint8) if target.dtype == torch.bool else target
+            where = (*_lift3(t.shape[2:]), *_lift3(z.shape[2:]), _DS_TKIND[target.dtype])
+        else:
+            t = target.contiguous()
+            where = (V,)
+        rows = (B * C,) if kind == "bce" else (B, C)      # how the entry points take the planes
+        name = f"dice_{kind}_ds" if level else f"dice_{kind}"
+        tbytes = z.numel() * t.element_size()             # the level's voxels, not the target's
         lib = N.lib()
-        nchunk = lib.fz_dice_bce_chunks(V)
-        part = torch.empty((planes, nchunk, 4), dtype=z.dtype, device=z.device)
+        part = torch.empty((rows[0], lib.fz_dice_bce_chunks(V), 4 if kind == "bce" else 3 * C + 1), dtype=z.dtype, device=z.device)
         with torch.cuda.device(z.device):
-            rc = Fn._timed("dice_bce_sums", 8 * z.numel(), lambda: lib.fz_dice_bce_sums(
-                z.data_ptr(), t.data_ptr(), part.data_ptr(), planes, V, N.stream_ptr(z)), cols=z.shape[0] * V)
-        N.check(rc, "fz_dice_bce_sums")
-        loss, coef = _bce_finish(part, planes, V, smooth)
+            rc = Fn._timed(name + "_sums", 4 * z.numel() + tbytes, lambda: getattr(lib, f"fz_{name}_sums")(
+                z.data_ptr(), t.data_ptr(), part.data_ptr(), *rows, *where, N.stream_ptr(z)), cols=B * V)
+        N.check(rc, f"fz_{name}_sums")
+        loss, coef = _bce_finish(part, B * C, V, smooth) if kind == "bce" else _ce_finish(part, B, C, V, smooth)
         ctx.save_for_backward(z, t, coef)
-        ctx.dims = (planes, V)
+        ctx.call = (name, rows, where, 1.0 / (B * C), 1.0 / (rows[0] * V), tbytes, B * V)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         z, t, coef = ctx.saved_tensors
-        planes, V = ctx.dims
+        name, rows, where, cd, cb, tbytes, cols = ctx.call
         gz = torch.empty_like(z)
         gs = g.reshape(1).to(z.dtype).contiguous()
         with torch.cuda.device(z.device):
-            rc = Fn._timed("dice_bce_grad", 12 * z.numel(), lambda: N.lib().fz_dice_bce_grad(
-                z.data_ptr(), t.data_ptr(), coef.data_ptr(), gz.data_ptr(), planes, V, 1.0 / planes,
-                1.0 / (planes * V), gs.data_ptr(), N.stream_ptr(z)), cols=z.shape[0] * V)
-        N.check(rc, "fz_dice_bce_grad")
-        return gz, None, None
+            rc = Fn._timed(name + "_grad", 8 * z.numel() + tbytes, lambda: getattr(N.lib(), f"fz_{name}_grad")(
+                z.data_ptr(), t.data_ptr(), coef.data_ptr(), gz.data_ptr(), *rows, *where, cd, cb, gs.data_ptr(),
+                N.stream_ptr(z)), cols=cols)
+        N.check(rc, f"fz_{name}_grad")
+        return gz, None, None, None, None
+
+
+def _shape_gate(logits, c_min, c_max, v_end=None):
+    """The shape conditions of the native passes, stated here only: c_min <= C <= c_max channels and V voxels per plane a
+    positive multiple of 4 (below v_end).  None, or (key, reason) of the first one missed, worded for the warning of a
+    deep-supervision level — the dense losses only ask whether there is one."""
+    B, C = logits.shape[:2]
+    if not (c_min <= C and (c_max is None or C <= c_max)):
+        return "channels", f"C = {C} (native: {c_min} <= C <= {c_max})"
+    V = logits.numel() // max(B * C, 1)
+    if V == 0 or V % 4 or (v_end is not None and V >= v_end):
+        return "voxels", f"{V} level voxels (native: a multiple of 4 below 2^31)"
+    return None
 
 
 def _fp32_logits(logits, target):
@@ -105,16 +141,19 @@ def _fp32_logits(logits, target):
     return logits, target
 
 
-def dice_bce_loss(logits, target, smooth: float = 1e-5):
+def _dense_loss(name, kind, composed, c_min, c_max, logits, target, smooth):
+    """the loss of a target at the logits' extents: native for fp32 device tensors that pass `_shape_gate`, else `composed`"""
     logits, target = _fp32_logits(logits, target)
-    planes = logits.shape[0] * logits.shape[1]
-    if logits.is_cuda and logits.numel() and logits.dtype == torch.float32 and target.dtype == torch.float32 \
-            and (logits.numel() // planes) % 4 == 0:
-        return DiceBCEFn.apply(logits, target, smooth)
+    if logits.is_cuda and logits.dtype == torch.float32 and _shape_gate(logits, c_min, c_max) is None:
+        return DiceLossFn.apply(logits, target, smooth, kind, False)
     if logits.is_cuda and logits.numel():
         from .composed import warn_once
-        warn_once("dice_bce_loss", f"no native kernel for shape {tuple(logits.shape)} / {logits.dtype}: composed framework ops")
-    return dice_bce_loss_composed(logits, target, smooth)
+        warn_once(name, f"no native kernel for shape {tuple(logits.shape)} / {logits.dtype}: composed framework ops")
+    return composed(logits, target, smooth)
+
+
+def dice_bce_loss(logits, target, smooth: float = 1e-5):
+    return _dense_loss("dice_bce_loss", "bce", dice_bce_loss_composed, 1, None, logits, target, smooth)
 
 
 # ---- the recipe's loss: DiceCELoss(sigmoid=True, squared_pred=True), MONAI 1.4 semantics -------------------
@@ -133,52 +172,11 @@ def dice_ce_loss_composed(logits, target, smooth: float = 1e-5):
     return _dice_term(logits, target, smooth) + F.cross_entropy(logits, target)
 
 
-class DiceCEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, smooth):
-        z = logits.contiguous()
-        t = target.contiguous()
-        B, C = z.shape[:2]
-        V = z.numel() // (B * C)
-        lib = N.lib()
-        nchunk = lib.fz_dice_bce_chunks(V)
-        part = torch.empty((B, nchunk, 3 * C + 1), dtype=z.dtype, device=z.device)
-        with torch.cuda.device(z.device):
-            rc = Fn._timed("dice_ce_sums", 8 * z.numel(), lambda: lib.fz_dice_ce_sums(
-                z.data_ptr(), t.data_ptr(), part.data_ptr(), B, C, V, N.stream_ptr(z)), cols=B * V)
-        N.check(rc, "fz_dice_ce_sums")
-        loss, coef = _ce_finish(part, B, C, V, smooth)
-        ctx.save_for_backward(z, t, coef)
-        ctx.dims = (B, C, V)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        z, t, coef = ctx.saved_tensors
-        B, C, V = ctx.dims
-        gz = torch.empty_like(z)
-        gs = g.reshape(1).to(z.dtype).contiguous()
-        with torch.cuda.device(z.device):
-            rc = Fn._timed("dice_ce_grad", 12 * z.numel(), lambda: N.lib().fz_dice_ce_grad(
-                z.data_ptr(), t.data_ptr(), coef.data_ptr(), gz.data_ptr(), B, C, V, 1.0 / (B * C),
-                1.0 / (B * V), gs.data_ptr(), N.stream_ptr(z)), cols=B * V)
-        N.check(rc, "fz_dice_ce_grad")
-        return gz, None, None
-
-
 def dice_ce_loss(logits, target, smooth: float = 1e-5):
     """``DiceCELoss(sigmoid=True, squared_pred=True)(logits, target)`` of the training recipe."""
-    B, C = logits.shape[:2]
-    if C == 1:
+    if logits.shape[1] == 1:
         return dice_bce_loss(logits, target, smooth)
-    logits, target = _fp32_logits(logits, target)
-    if logits.is_cuda and logits.numel() and logits.dtype == torch.float32 and 2 <= C <= 8 \
-            and (logits.numel() // (B * C)) % 4 == 0:
-        return DiceCEFn.apply(logits, target, smooth)
-    if logits.is_cuda and logits.numel():
-        from .composed import warn_once
-        warn_once("dice_ce_loss", f"no native kernel for shape {tuple(logits.shape)} / {logits.dtype}: composed framework ops")
-    return dice_ce_loss_composed(logits, target, smooth)
+    return _dense_loss("dice_ce_loss", "ce", dice_ce_loss_composed, 2, 8, logits, target, smooth)
 
 
 class DiceCELoss(torch.nn.Module):
@@ -199,12 +197,11 @@ class DiceCELoss(torch.nn.Module):
 # ---- deep supervision: MONAI 1.4 DeepSupervisionLoss over the head list of num_deep_supr networks --------------------
 # ushape.UNet returns one logits tensor per decoder level, finest first.  The loss of the list is Σ_l w_l · loss(z_l, t_l)
 # (not normalised) with t_l the target itself where the level has its extents and its nearest-exact down-sampling otherwise.
-# For an integer ratio r on an axis nearest-exact is the strided pick index = r·i + r//2, which csrc/loss_ds.hip applies as
+# For an integer ratio r on an axis nearest-exact is the strided pick index = r·i + r//2, which csrc/loss.hip applies as
 # an index map while it reads the full-resolution target: a coarse level then costs the launches of a dense one and writes
 # no target of its own.  (For non-integer ratios torch's float arithmetic and the integer formula floor((2i+1)·S_t/(2·S_l))
 # disagree — 26 -> 11 is the first case — so those are never computed natively.)
 _DS_MODES = ("same", "exp", "two")
-_DS_TKIND = {torch.float32: N.SEG_F32, torch.bfloat16: N.SEG_BF16, torch.uint8: N.SEG_U8, torch.bool: N.SEG_U8}
 
 
 def _ds_check_mode(weight_mode):
@@ -233,64 +230,8 @@ def ds_target_composed(target, size, dtype):
     return F.interpolate(target, size=tuple(size), mode="nearest-exact").to(dtype)
 
 
-def _lift3(spatial):
-    return (1,) * (3 - len(spatial)) + tuple(int(s) for s in spatial)
-
-
-class DiceCELevelFn(torch.autograd.Function):
-    """DiceCELoss of ONE coarse level against the full-resolution target (csrc/loss_ds.hip).  logits: fp32, contiguous or
-    not; target: as the caller holds it (fp32 / bf16 / uint8 / bool, contiguous) — saved as given, never resampled."""
-
-    @staticmethod
-    def forward(ctx, logits, target, smooth):
-        z = logits.contiguous()
-        t = target.view(torch.uint8) if target.dtype == torch.bool else target
-        B, C = z.shape[:2]
-        geom = (*_lift3(t.shape[2:]), *_lift3(z.shape[2:]), _DS_TKIND[target.dtype])
-        V = z.numel() // (B * C)
-        lib = N.lib()
-        nchunk = lib.fz_dice_bce_chunks(V)
-        tbytes = B * C * V * t.element_size()
-        if C == 1:
-            part = torch.empty((B, nchunk, 4), dtype=z.dtype, device=z.device)
-            with torch.cuda.device(z.device):
-                rc = Fn._timed("dice_bce_ds_sums", 4 * z.numel() + tbytes, lambda: lib.fz_dice_bce_ds_sums(
-                    z.data_ptr(), t.data_ptr(), part.data_ptr(), B, *geom, N.stream_ptr(z)), cols=B * V)
-            N.check(rc, "fz_dice_bce_ds_sums")
-            loss, coef = _bce_finish(part, B, V, smooth)
-        else:
-            part = torch.empty((B, nchunk, 3 * C + 1), dtype=z.dtype, device=z.device)
-            with torch.cuda.device(z.device):
-                rc = Fn._timed("dice_ce_ds_sums", 4 * z.numel() + tbytes, lambda: lib.fz_dice_ce_ds_sums(
-                    z.data_ptr(), t.data_ptr(), part.data_ptr(), B, C, *geom, N.stream_ptr(z)), cols=B * V)
-            N.check(rc, "fz_dice_ce_ds_sums")
-            loss, coef = _ce_finish(part, B, C, V, smooth)
-        ctx.save_for_backward(z, t, coef)
-        ctx.dims = (B, C, V, geom, tbytes)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        z, t, coef = ctx.saved_tensors
-        B, C, V, geom, tbytes = ctx.dims
-        gz = torch.empty_like(z)
-        gs = g.reshape(1).to(z.dtype).contiguous()
-        lib = N.lib()
-        with torch.cuda.device(z.device):
-            if C == 1:
-                rc = Fn._timed("dice_bce_ds_grad", 8 * z.numel() + tbytes, lambda: lib.fz_dice_bce_ds_grad(
-                    z.data_ptr(), t.data_ptr(), coef.data_ptr(), gz.data_ptr(), B, *geom, 1.0 / B, 1.0 / (B * V),
-                    gs.data_ptr(), N.stream_ptr(z)), cols=B * V)
-            else:
-                rc = Fn._timed("dice_ce_ds_grad", 8 * z.numel() + tbytes, lambda: lib.fz_dice_ce_ds_grad(
-                    z.data_ptr(), t.data_ptr(), coef.data_ptr(), gz.data_ptr(), B, C, *geom, 1.0 / (B * C), 1.0 / (B * V),
-                    gs.data_ptr(), N.stream_ptr(z)), cols=B * V)
-        N.check(rc, "fz_dice_bce_ds_grad" if C == 1 else "fz_dice_ce_ds_grad")
-        return gz, None, None
-
-
 def ds_level_launches(B: int, C: int, backward: bool = False) -> int:
-    """native launches of one sampled level: the sums pass, plus fz_dice_ce_finish where DiceCEFn runs it too (C >= 2 and
+    """native launches of one sampled level: the sums pass, plus fz_dice_ce_finish where the dense loss runs it too (C >= 2 and
     B <= 8; the other finishes are framework reductions of the partials); the backward is one gradient pass"""
     if backward:
         return 1
@@ -298,17 +239,14 @@ def ds_level_launches(B: int, C: int, backward: bool = False) -> int:
 
 
 def _ds_level_gate(loss, logits, target):
-    """None when csrc/loss_ds.hip takes this coarse level, else (key, reason) of the composed branch"""
+    """None when csrc/loss.hip takes this coarse level, else (key, reason) of the composed branch"""
     if not isinstance(loss, DiceCELoss):
         return "loss", f"{type(loss).__name__} is not ft.DiceCELoss"
     if logits.dtype not in (torch.float32, torch.bfloat16):
         return "logits", f"{logits.dtype} logits"
-    B, C = logits.shape[:2]
-    if not 1 <= C <= 8:
-        return "channels", f"C = {C} (native: 1 <= C <= 8)"
-    V = logits.numel() // max(B * C, 1)
-    if V == 0 or V % 4 or V >= 2 ** 31:
-        return "voxels", f"{V} level voxels (native: a multiple of 4 below 2^31)"
+    why = _shape_gate(logits, 1, 8, 2 ** 31)
+    if why is not None:
+        return why
     if len(logits.shape) > 5 or any(st % sl for st, sl in zip(target.shape[2:], logits.shape[2:])):
         return "ratio", f"target {tuple(target.shape[2:])} over level {tuple(logits.shape[2:])} is not an integer ratio"
     if target.dtype not in _DS_TKIND or not target.is_contiguous():
@@ -321,7 +259,7 @@ def deep_supervision_loss(inputs, target, loss=None, weight_mode: str = "exp", w
     list of logits (B, C, *S_l), finest first — what ``Factorizer(..., num_deep_supr=k)`` / ``Deconver(..., num_deep_supr=k)``
     return.  A tensor, or a list of one tensor whose weight is 1 (every mode gives that), is ``loss(input, target)`` itself.
     On a device, with ``ft.DiceCELoss``, a coarse level reads the full-resolution target through the nearest-exact index map
-    (csrc/loss_ds.hip); a level the kernels do not take (`_ds_level_gate`) interpolates the target and calls `loss`."""
+    (csrc/loss.hip); a level the kernels do not take (`_ds_level_gate`) interpolates the target and calls `loss`."""
     loss = DiceCELoss() if loss is None else loss
     _ds_check_mode(weight_mode)   # a bad mode is refused whatever the input is
     if isinstance(inputs, torch.Tensor):
@@ -344,7 +282,8 @@ def deep_supervision_loss(inputs, target, loss=None, weight_mode: str = "exp", w
         else:
             why = _ds_level_gate(loss, z, target) if z.is_cuda else ("cpu", "")
             if why is None:
-                term = DiceCELevelFn.apply(z.float() if z.dtype != torch.float32 else z, target, loss.smooth)
+                term = DiceLossFn.apply(z.float() if z.dtype != torch.float32 else z, target, loss.smooth,
+                                        "bce" if z.shape[1] == 1 else "ce", True)
             else:
                 if z.is_cuda:
                     from .composed import warn_once

@@ -66,7 +66,7 @@ def test_composed_target_is_the_strided_pick(dt, St, S):
 
 
 def test_nearest_exact_is_r_i_plus_half_r_for_integer_ratios_only():
-    """what csrc/loss_ds.hip relies on: torch's nearest-exact picks r·i + r//2 for every integer ratio, and NOT
+    """what the level reader of csrc/loss.hip relies on: torch's nearest-exact picks r·i + r//2 for every integer ratio, and NOT
     floor((2i+1)·S_t / (2·S_l)) for the others (first at 26 -> 11) — those are never computed natively"""
     for r in range(1, 17):
         for S in range(1, 129):

@@ -1,4 +1,4 @@
-"""-m gpu: csrc/loss_ds.hip behind ft.DeepSupervisionLoss / ft.deep_supervision_loss against the float64 reference of
+"""-m gpu: the level kernels of csrc/loss.hip behind ft.DeepSupervisionLoss / ft.deep_supervision_loss against the float64 reference of
 tests/ds_cases.py (strided slices of the target, then the composed loss), at the smallest shapes at which the index map
 can go wrong: 1-D, 2-D and 3-D levels, ratios 1 .. 4 mixed over the axes, level rows shorter than the 4 elements a thread
 walks, the kernel finish at B <= 8 and the framework finish at B = 9, one chunk and two.  Bounds: ds_cases.check."""
@@ -239,7 +239,7 @@ def test_launch_counts(geom, B, C):
 @pytest.mark.parametrize("St,S,C", [((26, 8), (11, 4), 3), ((20,), (8,), 1)])
 def test_non_integer_ratio_level_is_composed_warns_once_and_meets_the_bounds(St, S, C):
     """26 -> 11 is the first extent at which the integer formula and torch's nearest-exact disagree: such a level adds no launch
-    of csrc/loss_ds.hip — it interpolates the target (framework kernels) and runs the dense loss kernels on the result"""
+    of the level kernels of csrc/loss.hip — it interpolates the target (framework kernels) and runs the dense loss kernels on the result"""
     g = torch.Generator().manual_seed(13)
     zs = [torch.randn(2, C, *St, generator=g) * 3, torch.randn(2, C, *S, generator=g) * 3]
     t = (torch.rand(2, C, *St, generator=g) > 0.5).float()

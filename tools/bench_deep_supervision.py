@@ -1,4 +1,4 @@
-"""Device time per call, forward + backward, of the deep-supervision loss (ft.DeepSupervisionLoss, csrc/loss_ds.hip) against
+"""Device time per call, forward + backward, of the deep-supervision loss (ft.DeepSupervisionLoss, the level reader of csrc/loss.hip) against
 what the package offered before it (profiles/deep_supervision.md), at the head sizes of the two bundles:
 
     brats   B = 2,  C = 3, levels 128^3 / 64^3 / 32^3, uint8 target at 128^3

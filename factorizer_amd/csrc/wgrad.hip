@@ -504,6 +504,15 @@ static int wgrad_plan(const fz_wgrad_desc* d, void* workspace, WgradPlan<AT>& pl
     return fail(FZ_E_SHAPE, "fz_wgrad: 2-D s2d shape (K = 4*Cin, (H, W) = 2*(Ho, Wo), even Wo, N = Ho*Wo)");
   if (d->loader == QL_K3_2D && (d->K != 9 * d->Cin || d->H < 1 || d->W < 1 || d->N != (int64_t)d->H * d->W || d->Vq != d->N))
     return fail(FZ_E_SHAPE, "fz_wgrad: 2-D k3 shape (K = 9*Cin, N = Vq = H*W)");
+  // what the kernels would ignore is refused: they read q[0] and q[1] only, never src_mode, and the s2d / k3 loaders read
+  // q[0] alone and apply neither the statistics nor the activation (commit_tiles: QL_PLAIN only)
+  if (d->nsrc < 1 || d->nsrc > 2) return fail(FZ_E_UNSUPPORTED, "fz_wgrad: one or two input sources (nsrc)");
+  if (d->src_mode != 0) return fail(FZ_E_UNSUPPORTED, "fz_wgrad: src_mode must be 0 (two sources are a channel concat at c0)");
+  if (d->loader != QL_PLAIN && (d->nsrc != 1 || d->stats || d->qact))
+    return fail(FZ_E_UNSUPPORTED, "fz_wgrad: an s2d / k3 loader takes one source and no Q prologue (stats, qact)");
+  if (d->nsrc == 1 && d->c0 != 0) return fail(FZ_E_UNSUPPORTED, "fz_wgrad: c0 must be 0 with one source (the loaders split the channels at c0)");
+  if (d->nsrc == 2 && !d->q[1]) return fail(FZ_E_ARG, "fz_wgrad: null pointer (second source)");
+  if (d->nsrc == 2 && (d->c0 <= 0 || d->c0 >= d->Cin)) return fail(FZ_E_UNSUPPORTED, "fz_wgrad: two sources split inside (0, Cin) (c0)");
   if (d->N % 4 != 0) return fail(FZ_E_UNSUPPORTED, "fz_wgrad: column count must be a multiple of 4");
   if (d->loader == QL_S2D && ((d->Wo & 1) || d->K != 8 * d->Cin)) return fail(FZ_E_SHAPE, "fz_wgrad: s2d shape");
   if (d->loader == QL_K3 && d->K != 27 * d->Cin) return fail(FZ_E_SHAPE, "fz_wgrad: k3 shape");

@@ -543,8 +543,10 @@ typedef struct fz_wgrad_desc {
   int M;
   const void* pmul;   /* activation, optional: P *= act'(pmul)                                      */
   int pmul_kind;      /* FZ_ACT_RELU / FZ_ACT_GELU                                           */
-  const void* q[4];   /* activation: input sources                                                 */
-  int nsrc, src_mode, c0;
+  const void* q[4];   /* activation: input sources; q[0] and, with nsrc == 2, q[1] are read                */
+  int nsrc, src_mode, c0; /* nsrc 1 or 2; src_mode 0; nsrc == 1: c0 = 0; nsrc == 2: channel concat, q[0] holds channels [0, c0),
+                           * 0 < c0 < Cin.  The s2d / k3 loaders take nsrc == 1 and neither stats nor qact.  Outside that:
+                           * FZ_E_UNSUPPORTED (the 2-D loaders with a second source, stats or qact, and a null q[1]: FZ_E_ARG). */
   int Cin;            /* input channels                                                      */
   int K;              /* Q rows: Cin / 8*Cin / 27*Cin (2-D: 4*Cin / 9*Cin)                   */
   int64_t Vq;         /* voxels per sample of the input                                      */

@@ -261,6 +261,7 @@ _SIGS.update({
     "fz_conv3_fwd2": ([_vp] * 4 + [_i] * 8 + [_c.POINTER(BlockPrologue), _vp], _i),
     "fz_upcat2": ([_vp, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_c.POINTER(BlockPrologue), _vp], _i),
     "fz_gemm": ([_c.POINTER(GemmDesc), _vp], _i),
+    "fz_gemm_plan": ([_c.POINTER(GemmDesc), _c.c_char_p, _i], _i),
     "fz_gemm_bx_enable": ([_i], _i),
     "fz_gemm_lnbwd_partials": ([_c.POINTER(GemmDesc)], _i64),
     "fz_reduce_rows": ([_vp, _i64, _i, _vp, _vp, _vp], _i),

@@ -1,6 +1,8 @@
 // api.hip — library-level entry points of the C ABI (include/factorizer_hip.h).
 #include "fz_common.h"
 
+#include <cstdarg>
+
 namespace fz {
 std::string& last_error() {
   static thread_local std::string s;
@@ -13,6 +15,17 @@ std::atomic<int64_t>& launch_counter() {
 int& tile_order_ref() {
   static thread_local int v = 0;
   return v;
+}
+GemmPlan& gemm_plan() {
+  static thread_local GemmPlan p = {false, {0}};
+  return p;
+}
+int gemm_plan_form(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(gemm_plan().form, sizeof(gemm_plan().form), fmt, ap);
+  va_end(ap);
+  return FZ_OK;
 }
 }  // namespace fz
 

@@ -26,6 +26,17 @@ inline int fail(int code, const char* msg) {
   return code;
 }
 
+// Dry run of fz_gemm's dispatcher (fz_gemm_plan, gemm.hip).  While `only` is set on this thread, every launch site that
+// fz_gemm can reach writes the name of the kernel form it selected (family, template choices, grid) into `form` through
+// gemm_plan_form and returns without launching: the dry run IS the dispatcher, not a copy of its decisions.
+struct GemmPlan { bool only; char form[192]; };
+GemmPlan& gemm_plan();
+inline bool gemm_plan_only() { return gemm_plan().only; }
+int gemm_plan_form(const char* fmt, ...) __attribute__((format(printf, 1, 2)));   // records the form; returns FZ_OK
+inline const char* gemm_loader_name(int l) { const char* n[] = {"plain", "s2d", "k3", "s2d2", "k3_2"}; return n[l]; }
+inline const char* gemm_epi_name(int e) { const char* n[] = {"", " d2s", " lnbwd", " d2s2"}; return n[e]; }
+inline const char* gemm_pro_name(int p) { const char* n[] = {"", " ln", " gelu", " bmul"}; return n[p]; }   // PRO_* and BXPRO_* agree
+
 // Diagnostic environment knobs exist only in PROBE builds of the library (-DFZ_PROBE: tools/probes/build_alt.py builds a
 // second .so, loaded through FZ_LIB_PATH for same-box A/B runs).  The shipped library reads ONE environment variable,
 // FZ_GEMM_BX (the process default of the `products` descriptor field; both settings are valid results), and nothing else:

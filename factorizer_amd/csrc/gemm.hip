@@ -289,6 +289,31 @@ static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
   if (d->nsrc < 1 || d->nsrc > 2 || d->src_mode != 0)
     return fail(FZ_E_UNSUPPORTED, "fz_gemm: one source, or two sources concatenated along channels");
   if (d->bmul && d->bmul_kind != ACT_RELU) return fail(FZ_E_UNSUPPORTED, "fz_gemm: bmul supports the ReLU gate");
+  // (the gate is applied as the operand is fetched: in front of a LayerNorm or an activation it would gate their INPUT, which
+  // is not what the header promises and what no layer asks for; the streaming kernels refuse the pairing anyway)
+  if (d->bmul && (d->ln || d->bact)) return fail(FZ_E_UNSUPPORTED, "fz_gemm: bmul with a LayerNorm or activation prologue");
+  // ---- no field is dropped: what no kernel of the family reads for this loader / epilogue is refused, and so is what would
+  // send a kernel through a null pointer (fetch_plain reads x[1] for every channel >= c0) ----
+  if (d->nsrc == 2 && !d->x[1]) return fail(FZ_E_ARG, "fz_gemm: two sources need x[1]");
+  if (d->nsrc == 2 && (d->c0 <= 0 || d->c0 >= d->Cin))
+    return fail(FZ_E_UNSUPPORTED, "fz_gemm: two sources need 0 < c0 < Cin (x[0] holds c0 channels, x[1] the other Cin - c0)");
+  if (d->nsrc == 1 && d->c0 != 0 && d->c0 != d->Cin) return fail(FZ_E_UNSUPPORTED, "fz_gemm: one source takes c0 = 0 (or Cin)");
+  if (d->bact < ACT_NONE || d->bact > ACT_GELU || d->eact < ACT_NONE || d->eact > ACT_GELU || (d->emul && (d->emul_kind < ACT_NONE || d->emul_kind > ACT_GELU)))
+    return fail(FZ_E_ARG, "fz_gemm: bact / eact / emul_kind must be FZ_ACT_NONE, FZ_ACT_RELU or FZ_ACT_GELU");
+  if (d->ln && (!d->ln_g || !d->ln_b)) return fail(FZ_E_ARG, "fz_gemm: the LayerNorm prologue needs ln_g and ln_b");
+  // (every kernel folds the LayerNorm affine into its staged weights, W·diag(γ) and W·β: an activation would have to sit between
+  // the affine and the product.  The resident and the persistent kernel used to accept the pair and compute W·(γ ∘ act(x̂)) + W·β)
+  if (d->ln && d->bact) return fail(FZ_E_UNSUPPORTED, "fz_gemm: an input activation behind the LayerNorm prologue is not computed");
+  // (gemm_chain64_kernel reads no input activation; the M = 32 form on the resident kernel applies it)
+  if (lnb64 && d->bact)
+    return fail(FZ_E_UNSUPPORTED, "fz_gemm: the 64-channel LayerNorm-backward epilogue takes no input activation");
+  if (d->stats_out && !d->ln) return fail(FZ_E_UNSUPPORTED, "fz_gemm: stats_out without the LayerNorm prologue (nothing writes it)");
+  if (d->epilogue == EPI_D2S && (d->eact || d->emul))
+    return fail(FZ_E_UNSUPPORTED, "fz_gemm: depth-to-space epilogue takes bias and res, no eact / emul");
+  // (store_block's depth-to-space form has no W·β row term: the resident kernel used to accept the pair and drop β)
+  if (d->epilogue == EPI_D2S && d->ln) return fail(FZ_E_UNSUPPORTED, "fz_gemm: depth-to-space epilogue behind a LayerNorm prologue");
+  if ((d->loader == LOAD_S2D || d->loader == LOAD_K3) && d->bact)
+    return fail(FZ_E_UNSUPPORTED, "fz_gemm: space-to-depth and k3 loaders take no input activation");
   if (d->B == 0) return FZ_OK;
   GemmArgsT<AT> a;
   for (int i = 0; i < 4; ++i) a.x[i] = (const AT*)d->x[i];
@@ -358,18 +383,23 @@ static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
     const size_t lds = (size_t)(nA * RB * 64 + 32 * RB + (d->epilogue == EPI_LNBWD ? 256 : 0)) * sizeof(float);
     const int64_t tiles = (d->Ncol + 511) / 512;
     dim3 grid((unsigned)(tiles * d->B), (unsigned)((mblocks + RB - 1) / RB)), block(256);
-#define FZ_RES_PF(NS, E, BM, PFv) hipLaunchKernelGGL((gemm_resident_kernel<NS, E, BM, false, AT, PFv>), grid, block, lds, st, a, RB)
+// (fz_gemm_plan's dry run, fz_common.h: the form is named and nothing is launched)
+#define FZ_RES_FORM(NS, E, PFv, EXTRA)                                                                                          \
+  if (gemm_plan_only())                                                                                                       \
+    return gemm_plan_form("resident ns%d plain%s pf%d%s rb=%d grid=%ux%u", NS, gemm_epi_name(E), PFv, EXTRA, RB, grid.x, grid.y)
+#define FZ_RES_PF(NS, E, BM, PFv)                                                                                              \
+  do { FZ_RES_FORM(NS, E, PFv, BM ? " bmul" : ""); hipLaunchKernelGGL((gemm_resident_kernel<NS, E, BM, false, AT, PFv>), grid, block, lds, st, a, RB); } while (0)
 #define FZ_RES(NS, E, BM)                                                  \
   do {                                                                    \
     const int pf = (d->bact ? 1 : 0) | (d->ln ? 2 : 0);                   \
     if (pf == 0) FZ_RES_PF(NS, E, BM, 0);                                 \
     else if (pf == 1) FZ_RES_PF(NS, E, BM, 1);                            \
-    else if (pf == 2) FZ_RES_PF(NS, E, BM, 2);                            \
-    else FZ_RES_PF(NS, E, BM, 3);                                         \
+    else FZ_RES_PF(NS, E, BM, 2); /* (pf 3, LayerNorm + activation, is refused in gemm_launch) */ \
   } while (0)
     if (d->epilogue == EPI_LNBWD) {
       if (d->bmul) return fail(FZ_E_UNSUPPORTED, "fz_gemm: bmul with LayerNorm-backward epilogue");
-#define FZ_RES_LNB(NS, GA) hipLaunchKernelGGL((gemm_resident_kernel<NS, EPI_LNBWD, false, GA>), grid, block, lds, st, a, RB)
+#define FZ_RES_LNB(NS, GA)                                                                                                     \
+  do { FZ_RES_FORM(NS, EPI_LNBWD, 3, GA ? " gadd" : ""); hipLaunchKernelGGL((gemm_resident_kernel<NS, EPI_LNBWD, false, GA>), grid, block, lds, st, a, RB); } while (0)
       if (d->lnb_gadd) { if (nA <= 16) FZ_RES_LNB(16, true); else FZ_RES_LNB(32, true); }
       else { if (nA <= 16) FZ_RES_LNB(16, false); else FZ_RES_LNB(32, false); }
     } else if (d->epilogue == EPI_D2S) {
@@ -378,8 +408,9 @@ static int gemm_launch(const fz_gemm_desc* d, fz_stream_t stream) {
     } else if (d->bmul) {
       if (nA <= 16) FZ_RES(16, EPI_PLAIN, true); else FZ_RES(32, EPI_PLAIN, true);
     } else if (d->res && !d->emul && d->M == 32 && nA <= 16 && !d->ln && knob_res_prefetch()) {
-      if (d->bact) hipLaunchKernelGGL((gemm_resident_kernel<16, EPI_PLAIN, false, false, AT, 1, true>), grid, block, lds, st, a, RB);
-      else hipLaunchKernelGGL((gemm_resident_kernel<16, EPI_PLAIN, false, false, AT, 0, true>), grid, block, lds, st, a, RB);
+#define FZ_RES_RESPF(PFv)                                                                                                      \
+  do { FZ_RES_FORM(16, EPI_PLAIN, PFv, " respf"); hipLaunchKernelGGL((gemm_resident_kernel<16, EPI_PLAIN, false, false, AT, PFv, true>), grid, block, lds, st, a, RB); } while (0)
+      if (d->bact) FZ_RES_RESPF(1); else FZ_RES_RESPF(0);
     } else {
       if (nA <= 16) FZ_RES(16, EPI_PLAIN, false); else FZ_RES(32, EPI_PLAIN, false);
     }
@@ -396,6 +427,18 @@ extern "C" int fz_gemm(const fz_gemm_desc* d, fz_stream_t stream) {
   if (d->act_dtype == FZ_STORE_F32) return gemm_launch<float>(d, stream);
   if (d->act_dtype == FZ_STORE_BF16) return gemm_launch<bf16>(d, stream);
   return fail(FZ_E_ARG, "fz_gemm: act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
+}
+
+// Dry run: fz_gemm itself with this thread's plan flag set — every launch site names its form and returns in place of
+// launching (gemm_plan_only, fz_common.h), so the form reported is the form fz_gemm launches.
+extern "C" int fz_gemm_plan(const fz_gemm_desc* d, char* form, int cap) {
+  GemmPlan& pl = gemm_plan();
+  pl.only = true;
+  pl.form[0] = 0;
+  const int rc = fz_gemm(d, nullptr);
+  pl.only = false;
+  if (form && cap > 0) snprintf(form, (size_t)cap, "%s", rc == FZ_OK ? pl.form : "");
+  return rc;
 }
 
 extern "C" int64_t fz_gemm_lnbwd_partials(const fz_gemm_desc* d) {

@@ -384,6 +384,9 @@ int gemm_bx_launch(const GemmArgsT<AT>& a0, int loader, int epilogue, int pro, f
   const bool wt = a.w_t != 0;
 #define FZ_BX(MBv, NAv, L, E, PR, RDv)                                                                           \
   do {                                                                                                           \
+    if (gemm_plan_only())                                                                                        \
+      return gemm_plan_form("bx_stream mb%d nacc%d %s%s%s%s rd%d grid=%ux%u", MBv, NAv, gemm_loader_name(L),       \
+                            gemm_epi_name(E), gemm_pro_name(PR), wt ? " wt" : "", RDv, grid.x, grid.y);           \
     if (wt) hipLaunchKernelGGL((gemm_bx_kernel<MBv, NAv, L, E, PR, RDv, true, AT>), grid, block, 0, st, a);      \
     else hipLaunchKernelGGL((gemm_bx_kernel<MBv, NAv, L, E, PR, RDv, false, AT>), grid, block, 0, st, a);        \
   } while (0)

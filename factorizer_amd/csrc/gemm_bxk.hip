@@ -357,6 +357,9 @@ int gemm_bxk_launch(const GemmArgsT<AT>& a0, int loader, int epilogue, int pro, 
   const bool wt = a.w_t != 0;
 #define FZ_BXK(MBv, NAv, L, E, PR, RDv)                                                                            \
   do {                                                                                                             \
+    if (gemm_plan_only())                                                                                          \
+      return gemm_plan_form("bxk mb%d nacc%d %s%s%s%s rd%d grid=%ux%u", MBv, NAv, gemm_loader_name(L),               \
+                            gemm_epi_name(E), gemm_pro_name(PR), wt ? " wt" : "", (int)(RDv), grid.x, grid.y);      \
     if (wt) hipLaunchKernelGGL((gemm_bxk_kernel<MBv, NAv, L, E, PR, RDv, true, AT>), grid, block, 0, st, a);       \
     else hipLaunchKernelGGL((gemm_bxk_kernel<MBv, NAv, L, E, PR, RDv, false, AT>), grid, block, 0, st, a);         \
   } while (0)

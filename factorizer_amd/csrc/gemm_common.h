@@ -19,7 +19,7 @@ template <typename AT>
 struct GemmArgsT {
   const AT* x[4];      // input sources
   int nsrc;            // number of sources
-  int src_mode;        // 0: channel concat (x[0]: c0 channels, x[1]: Cin-c0)   1: average of sources
+  int src_mode;        // 0: channel concat (x[0]: c0 channels, x[1]: Cin-c0); gemm_launch refuses every other value
   int c0;
   int Cin;             // input channels
   int64_t Vin;         // voxels per sample of the input tensor(s)

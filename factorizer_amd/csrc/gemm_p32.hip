@@ -20,6 +20,7 @@ namespace fz {
 template <int PF, typename AT>
 __global__ __launch_bounds__(256, 2) void gemm_p32_kernel(GemmArgsT<AT> p, unsigned ntiles) {
   constexpr bool ACTIN = (PF & 1) != 0, LNP = (PF & 2) != 0;
+  // (only PF 0 and 2 are instantiated: gemm_p32_launch.  The ACTIN arms below are kept as the resident kernel's are, unreachable here)
   __shared__ float tW[32];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -158,11 +159,12 @@ int gemm_p32_launch(const fz_gemm_desc* d, const GemmArgsT<AT>& a, fz_stream_t s
   const unsigned ntiles = (unsigned)(d->B * ((d->Ncol + 127) / 128));
   const unsigned cap = (unsigned)knob_p32_wgs();
   const unsigned wgs = (ntiles + 3) / 4 < cap ? (ntiles + 3) / 4 : cap;
-  const int pf = (d->bact ? 1 : 0) | (d->ln ? 2 : 0);
+  // (gemm_launch sends no input activation here: alone it stays with the resident kernel, behind a LayerNorm it is refused)
+  const int pf = d->ln ? 2 : 0;
   dim3 grid(wgs), block(256);
+  if (gemm_plan_only()) return gemm_plan_form("p32 pf%d grid=%ux1", pf, grid.x);   // (fz_gemm_plan's dry run)
   if (pf == 0) hipLaunchKernelGGL((gemm_p32_kernel<0, AT>), grid, block, 0, st, a, ntiles);
-  else if (pf == 2) hipLaunchKernelGGL((gemm_p32_kernel<2, AT>), grid, block, 0, st, a, ntiles);
-  else hipLaunchKernelGGL((gemm_p32_kernel<3, AT>), grid, block, 0, st, a, ntiles);
+  else hipLaunchKernelGGL((gemm_p32_kernel<2, AT>), grid, block, 0, st, a, ntiles);
   FZ_LAUNCH_CHECK();
   return FZ_OK;
 }

@@ -63,7 +63,10 @@ __global__ __launch_bounds__(256, ((MB == 2 && NACC == 4 && PRO == 3 /* gate ope
   const int b = bx / tiles_per_sample;
   const int64_t n0 = ((int64_t)(bx % tiles_per_sample) * WT + (KS > 1 ? 0 : wave)) * TN;
   const int m0 = by * 32 * MB;
-  const int nA = (p.K + 1) / 2;
+  // A steps: two channels per step, and the space-to-depth loaders walk the taps of a channel PAIR together (a_k) — with an odd
+  // Cin the last pair is half empty but still takes all its tap steps ((K + 1) / 2 = 4·Cin stopped after taps 0..3 of the last
+  // channel; tests/test_gpu_gemm.py str_s2d); the empty half has zero weights (load_chunk: kk < K) and a masked operand
+  const int nA = LOADER == LOAD_S2D ? 8 * ((p.Cin + 1) / 2) : (LOADER == LOAD_S2D_2D ? 4 * ((p.Cin + 1) / 2) : (p.K + 1) / 2);
 
   if (PRO == PRO_LN) {
     // s[m] = Σ_k W[m][k]·γ[k], t[m] = Σ_k W[m][k]·β[k]: 8 threads per row, k interleaved (a single
@@ -449,12 +452,18 @@ int gemm_stream_launch(const fz_gemm_desc* d, GemmArgsT<AT> a, fz_stream_t strea
   a.xtiles = (int)(tiles * d->B);
   dim3 grid((unsigned)(tiles * d->B), (unsigned)ygr), block(256);
   if (a.ygroups > 1) grid = dim3((unsigned)(((tiles * d->B + 7) / 8) * 8 * ygr), 1);
-#define FZ_STR(MB, NA, L, E, PR) hipLaunchKernelGGL((gemm_stream_kernel<MB, NA, L, E, PR>), grid, block, 0, st, a)
-#define FZ_STRK(MB, NA, L, E, PR) hipLaunchKernelGGL((gemm_stream_kernel<MB, NA, L, E, PR, 4>), grid, block, 0, st, a)
+// (fz_gemm_plan's dry run, fz_common.h: the form is named and nothing is launched)
+#define FZ_STR_FORM(MB, NA, L, E, PR, KS)                                                                           \
+  if (gemm_plan_only())                                                                                             \
+    return gemm_plan_form("stream mb%d nacc%d %s%s%s%s grid=%ux%u", MB, NA, gemm_loader_name(L), gemm_epi_name(E),   \
+                          gemm_pro_name(PR), KS, grid.x, grid.y)
+#define FZ_STR(MB, NA, L, E, PR)                                                                                    \
+  do { FZ_STR_FORM(MB, NA, L, E, PR, ""); hipLaunchKernelGGL((gemm_stream_kernel<MB, NA, L, E, PR>), grid, block, 0, st, a); } while (0)
+#define FZ_STRK(MB, NA, L, E, PR)                                                                                   \
+  do { FZ_STR_FORM(MB, NA, L, E, PR, " ks4"); hipLaunchKernelGGL((gemm_stream_kernel<MB, NA, L, E, PR, 4>), grid, block, 0, st, a); } while (0)
   if (d->bact == ACT_RELU) return fail(FZ_E_UNSUPPORTED, "fz_gemm: ReLU input prologue is not compiled (streaming)");
   const int pro = d->ln ? PRO_LN : (d->bact == ACT_GELU ? PRO_GELU : (d->bmul ? PRO_BMUL : PRO_NONE));
-  if ((d->ln != 0) + (d->bact != 0) + (d->bmul != nullptr) > 1)
-    return fail(FZ_E_UNSUPPORTED, "fz_gemm: at most one input prologue (LayerNorm / GELU / gate)");
+  // (at most one of them is set: gemm_launch refuses bact behind ln and bmul beside either)
   if (d->loader == LOAD_S2D) { if (ks == 4) FZ_STRK(1, 2, LOAD_S2D, EPI_PLAIN, PRO_NONE); else FZ_STR(1, 2, LOAD_S2D, EPI_PLAIN, PRO_NONE); }
   else if (d->loader == LOAD_S2D_2D) { if (ks == 4) FZ_STRK(1, 2, LOAD_S2D_2D, EPI_PLAIN, PRO_NONE); else FZ_STR(1, 2, LOAD_S2D_2D, EPI_PLAIN, PRO_NONE); }
   else if (d->loader == LOAD_K3_2D) { if (MBsel == 2) FZ_STR(2, 4, LOAD_K3_2D, EPI_PLAIN, PRO_NONE); else FZ_STR(1, 4, LOAD_K3_2D, EPI_PLAIN, PRO_NONE); }

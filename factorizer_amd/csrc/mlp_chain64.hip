@@ -632,6 +632,8 @@ int chain64_lnb_launch(const fz_gemm_desc* d, const GemmArgsT<AT>& a, fz_stream_
   if (!d->lnb_gadd) return fail(FZ_E_UNSUPPORTED, "fz_gemm: the 64-channel LayerNorm-backward epilogue needs the added gradient");
   ChainArgsT<AT> c = {};
   const int ntiles = (int)fz_mlp_partials(d->B, d->Ncol);
+  if (gemm_plan_only())   // (fz_gemm_plan's dry run)
+    return gemm_plan_form("chain64_lnb %s grid=%dx1", products_split(d->products) ? "split" : "fp32", ntiles < 512 ? ntiles : 512);
   auto kern = products_split(d->products) ? gemm_chain64_kernel<true, AT, true, true> : gemm_chain64_kernel<true, AT, true, false>;
   return launch_lds(kern, dim3((unsigned)(ntiles < 512 ? ntiles : 512)), dim3(256), chain64_lds_floats(false, false),
                     (hipStream_t)stream, a, c, ntiles);

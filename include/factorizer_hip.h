@@ -55,7 +55,7 @@ int fz_version(void);
  * compares fz_abi_version() with the FZ_ABI_VERSION of the header it was written against BEFORE the first call and refuses
  * to run on a mismatch (factorizer_amd/_native.py does).  History: 3 = round 3; 4 = round 4 (`products` / `tune` descriptor
  * fields, `products` argument of fz_conv3_*); 5 = round 5 (the two-window entry points fz_nmf_cf_fwd2 / _bwd2 removed, this
- * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words; fz_gcorr_act / fz_gcorr_wgrad_act / fz_gcorr_mu_bwd: the grouped correlations on bf16 storage; fz_dice_bce_ds_* / fz_dice_ce_ds_*: the deep-supervision levels of the loss) leave it at 7. */
+ * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words; fz_gcorr_act / fz_gcorr_wgrad_act / fz_gcorr_mu_bwd: the grouped correlations on bf16 storage; fz_dice_bce_ds_* / fz_dice_ce_ds_*: the deep-supervision levels of the loss; fz_gemm_plan: the dry run of fz_gemm's dispatcher) leave it at 7. */
 #define FZ_ABI_VERSION 7
 int fz_abi_version(void);
 /* Walking order of the fused-core launches (fz_nmf_cf_fwd / fz_nmf_cf_bwd) this THREAD issues from now on: 0 = ascending over
@@ -261,7 +261,6 @@ int fz_act_add(void* dst, const void* src, int64_t n, int act_dtype, fz_stream_t
  *   Linear (Conv1d k=1 on flatten(2))      layers/linear.py:53-58
  *   LayerNorm over channels as a prologue  layers/norm.py:29-34
  *   MLP Linear-GELU-Linear                 layers/mlp.py:54-60
- *   window average of inverse_forward      factorization/operations.py:426-433 (src_mode 1)
  *   adapter on cat([skip, up])             unet.py:128 + factorizer.py:116 (two sources, no cat)
  *   Conv3d(k=2,s=2) downsample             unet.py:53   (loader = FZ_LOAD_S2D)
  *   ConvTranspose3d(k=2,s=2) upsample      unet.py:123  (epilogue = FZ_EPI_D2S)
@@ -292,16 +291,16 @@ int fz_act_add(void* dst, const void* src, int64_t n, int act_dtype, fz_stream_t
 #define FZ_PRODUCTS_FP32_MFMA 2  /* v_mfma_f32_32x32x2_f32 / _16x16x4_f32                                               */
 
 typedef struct fz_gemm_desc {
-  const void* x[4];    /* activation: input source tensors (B, C_i, Vin)                                */
-  int nsrc;            /* number of sources                                                    */
-  int src_mode;        /* 0: channel concat of x[0] (c0 ch) and x[1]; 1: average of nsrc sources */
-  int c0;              /* channels of x[0] in concat mode (0 = all)                            */
+  const void* x[4];    /* activation: input source tensors (B, C_i, Vin); x[0], and x[1] when nsrc == 2: x[2], x[3] are not read */
+  int nsrc;            /* number of sources: 1, or 2 (plain loader without bmul only)          */
+  int src_mode;        /* 0: channel concat of x[0] (c0 channels) and x[1] (Cin - c0); anything else: FZ_E_UNSUPPORTED */
+  int c0;              /* nsrc == 2: channels of x[0], 0 < c0 < Cin; nsrc == 1: 0 (or Cin)     */
   int Cin;             /* input channels                                                       */
   int64_t Vin;         /* voxels per sample of the input                                       */
   int Di, Hi, Wi;      /* input D, H, W (FZ_LOAD_S2D: fine grid; FZ_LOAD_K3)                   */
   const float* w;      /* weights                                                              */
   int w_t, ldw;        /* A[m][k] = w_t ? w[k*ldw + m] : w[m*ldw + k]                          */
-  int M, K;            /* output rows, reduction length (even)                                 */
+  int M, K;            /* output rows, reduction length (odd: plain loader without ln only)    */
   const float* bias;   /* [M] (plain) / [M/8] (d2s) / [M/4] (2-D d2s) or NULL                  */
   int ln;              /* LayerNorm prologue over Cin                                          */
   const float* ln_g;
@@ -344,6 +343,19 @@ int64_t fz_gemm_lnbwd_partials(const fz_gemm_desc* desc);
 int fz_reduce_rows(const float* part, int64_t rows, int n, float* out, float* tmp, fz_stream_t stream);
 
 int fz_gemm(const fz_gemm_desc* desc, fz_stream_t stream);
+/* No field of the descriptor is dropped silently.  Besides the pairings above fz_gemm refuses, before any launch:
+ *   FZ_E_ARG          nsrc == 2 with x[1] == NULL; ln without ln_g / ln_b; bact / eact / emul_kind outside FZ_ACT_*
+ *   FZ_E_UNSUPPORTED  nsrc == 2 with c0 outside (0, Cin); nsrc == 1 with c0 not in {0, Cin}; eact, emul or ln with FZ_EPI_D2S;
+ *                     stats_out without ln; bact with FZ_LOAD_S2D / FZ_LOAD_K3; bmul with ln or bact; bact with FZ_EPI_LNBWD at M = K = 64 (that kernel has no input activation); bact with ln
+ *                     (the LayerNorm affine is folded into the staged weights: nothing can act between them); more than one of ln / bact / bmul where the
+ *                     layer is not on the register-resident kernel (K <= 32), bact = FZ_ACT_RELU there likewise.
+ * Dry run of the dispatcher: the code fz_gemm runs up to, not including, the launch.  Returns what fz_gemm would return for
+ * this descriptor (same last-error string) and writes the name of the kernel form it would launch into form[cap]:
+ * family, template choices, then the launch geometry as key=value, e.g. "bx_stream mb2 nacc4 plain gelu wt rd1 grid=512x1",
+ * "bxk mb1 nacc1 plain rd4 grid=...", "resident ns16 plain pf2 rb=1 grid=...", "stream mb1 nacc2 s2d ks4 grid=...",
+ * "p32 pf2 grid=...", "head m4 grid=...", "chain64_lnb split grid=...".  Nothing is dereferenced and nothing is launched: the
+ * pointers need only be non-null and aligned as the real ones would be.  (tests/gemm_cases.py maps its cases to forms with it.) */
+int fz_gemm_plan(const fz_gemm_desc* desc, char* form, int cap);
 /* fz_gemm runs layers with a reduction length >= 64 on the bf16 matrix cores with every fp32 operand split into three
  * bf16 values and six exact products per fp32 product (csrc/gemm_bx.hip: fp32 accuracy at 6/16 of the fp32-MFMA time).
  * on = 0 keeps them on v_mfma_f32_32x32x2_f32, on = 1 enables, on < 0 only queries; returns the previous setting.

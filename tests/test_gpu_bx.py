@@ -46,8 +46,10 @@ def _lin_mag(x, w, b=None, res=None):
 
 
 LIN = [(2, 64, 64, (8, 8, 8)), (1, 128, 64, (8, 8, 4)), (2, 256, 512, (4, 4, 4)), (1, 1024, 512, (4, 4, 4)),
-       (1, 80, 96, (6, 4, 4)),      # K, M not multiples of 16 / 32, partial tiles
-       (2, 64, 32, (16, 16, 8)),    # wide tiles (NACC 4)
+       (1, 80, 96, (6, 4, 4)),      # K % 32 != 0: outside the split family (gemm_bx_ok) — BOTH settings run the fp32 streaming kernel
+       #                              (fz_gemm_plan: "stream mb1 nacc1 plain"), so this case compares that kernel with itself
+       (2, 64, 32, (16, 16, 8)),    # Ncol B = 4096: the K-split form at its narrowest tile (fz_gemm_plan: "bxk mb1 nacc1 plain rd4"),
+       #                              not the NACC-4 streaming forms: tests/test_gpu_gemm.py reaches those (bx_*_n4, bx_auto_n4_mb2)
        (1, 512, 1024, (8, 8, 8)),
        (1, 96, 64, (8, 8, 8))]      # K % 64 == 32: the trailing half chunk runs on zero weights
 

@@ -278,19 +278,25 @@ def nmf_decompose(x, u0, v0, T, G, solver, eps=1e-16):
     return NMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps)
 
 
-# ---- split-N NMF: matrices too wide for one wavefront (csrc/nmf_global.hip) -------
+# ---- split-N NMF: matrices too wide for one wavefront ----------------------------
+# two kernel families with one argument list: "gnmf" (csrc/nmf_global.hip: M <= 64, rank <= 4) and "gnmfx"
+# (csrc/nmf_global_rank.hip: 16 <= M <= 512, rank <= 32, MU / HALS)
 def gnmf_supported(M, N_, R, T, G) -> bool:
     return bool(N.lib().fz_gnmf_supported(int(M), int(N_), int(R), int(T), int(G)))
 
 
-def _gnmf_ws(x, nmat, M, Nn, R, T, backward):
-    nb = N.lib().fz_gnmf_workspace_bytes(nmat, M, Nn, R, T, int(backward))
+def gnmfx_supported(M, N_, R, T, G) -> bool:
+    return bool(N.lib().fz_gnmfx_supported(int(M), int(N_), int(R), int(T), int(G)))
+
+
+def _gnmf_ws(x, nmat, M, Nn, R, T, backward, fam="gnmf"):
+    nb = getattr(N.lib(), f"fz_{fam}_workspace_bytes")(nmat, M, Nn, R, T, int(backward))
     if nb < 0:
-        raise N.NativeError("fz_gnmf_workspace_bytes failed")
+        raise N.NativeError(f"fz_{fam}_workspace_bytes failed")
     return torch.empty(max(nb // 4, 1), dtype=torch.float32, device=x.device)
 
 
-def _gnmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=False):
+def _gnmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=False, fam="gnmf"):
     M, Nn = x.shape[-2:]
     R = u0.shape[1]
     nmat = x.numel() // (M * Nn)
@@ -299,74 +305,84 @@ def _gnmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=False):
     if want_uv:
         u = torch.empty((*x.shape[:-2], M, R), dtype=x.dtype, device=x.device)
         v = torch.empty((*x.shape[:-2], Nn, R), dtype=x.dtype, device=x.device)
-    ws = _gnmf_ws(x, nmat, M, Nn, R, T, False)
+    ws = _gnmf_ws(x, nmat, M, Nn, R, T, False, fam)
+    fwd = getattr(N.lib(), f"fz_{fam}_fwd")
     with _dev_guard(x):
-        rc = _timed(f"gnmf_fwd_{M}x{Nn}", 2 * x.numel() * 4, lambda: N.lib().fz_gnmf_fwd(
+        rc = _timed(f"{fam}_fwd_{M}x{Nn}", 2 * x.numel() * 4, lambda: fwd(
             x.data_ptr(), u0.data_ptr(), v0.data_ptr(), y.data_ptr(), N.ptr(u), N.ptr(v), nmat, M, Nn, R, T,
             N.SOLVER_ID[solver], eps, ws.data_ptr(), N.stream_ptr(x)))
-    N.check(rc, "fz_gnmf_fwd")
+    N.check(rc, f"fz_{fam}_fwd")
     return y, u, v
 
 
-def _gnmf_bwd_raw(x, u0, v0, gy, gu, gv, T, G, solver, eps):
+def _gnmf_bwd_raw(x, u0, v0, gy, gu, gv, T, G, solver, eps, fam="gnmf"):
     M, Nn = x.shape[-2:]
     R = u0.shape[1]
     nmat = x.numel() // (M * Nn)
     gx = torch.empty_like(x)
-    ws = _gnmf_ws(x, nmat, M, Nn, R, T, True)
+    ws = _gnmf_ws(x, nmat, M, Nn, R, T, True, fam)
+    bwd = getattr(N.lib(), f"fz_{fam}_bwd")
     with _dev_guard(x):
-        rc = _timed(f"gnmf_bwd_{M}x{Nn}", 3 * x.numel() * 4, lambda: N.lib().fz_gnmf_bwd(
+        rc = _timed(f"{fam}_bwd_{M}x{Nn}", 3 * x.numel() * 4, lambda: bwd(
             x.data_ptr(), u0.data_ptr(), v0.data_ptr(), N.ptr(gy), N.ptr(gu), N.ptr(gv), gx.data_ptr(), nmat, M, Nn,
             R, T, G, N.SOLVER_ID[solver], eps, ws.data_ptr(), N.stream_ptr(x)))
-    N.check(rc, "fz_gnmf_bwd")
+    N.check(rc, f"fz_{fam}_bwd")
     return gx
 
 
 class GNMFFn(torch.autograd.Function):
-    """y = u_T v_Tᵀ for matrices whose columns are split over workgroups."""
+    """y = u_T v_Tᵀ for matrices whose columns are split over workgroups (`fam`: the kernel family)."""
 
     @staticmethod
-    def forward(ctx, x, u0, v0, T, G, solver, eps):
+    def forward(ctx, x, u0, v0, T, G, solver, eps, fam):
         x, u0, v0 = x.contiguous(), u0.contiguous(), v0.contiguous()
-        y, _, _ = _gnmf_fwd_raw(x, u0, v0, T, solver, eps)
+        y, _, _ = _gnmf_fwd_raw(x, u0, v0, T, solver, eps, fam=fam)
         ctx.save_for_backward(x, u0, v0)
-        ctx.cfg = (T, G, solver, eps)
+        ctx.cfg = (T, G, solver, eps, fam)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, u0, v0 = ctx.saved_tensors
-        T, G, solver, eps = ctx.cfg
+        T, G, solver, eps, fam = ctx.cfg
         if G <= 0:
-            return torch.zeros_like(x), None, None, None, None, None, None
-        return _gnmf_bwd_raw(x, u0, v0, gy.contiguous(), None, None, T, G, solver, eps), None, None, None, None, None, None
+            return (torch.zeros_like(x), *[None] * 7)
+        return (_gnmf_bwd_raw(x, u0, v0, gy.contiguous(), None, None, T, G, solver, eps, fam), *[None] * 7)
 
 
 class GNMFDecomposeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, u0, v0, T, G, solver, eps):
+    def forward(ctx, x, u0, v0, T, G, solver, eps, fam):
         x, u0, v0 = x.contiguous(), u0.contiguous(), v0.contiguous()
-        _, u, v = _gnmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=True)
+        _, u, v = _gnmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=True, fam=fam)
         ctx.save_for_backward(x, u0, v0)
-        ctx.cfg = (T, G, solver, eps)
+        ctx.cfg = (T, G, solver, eps, fam)
         return u, v
 
     @staticmethod
     def backward(ctx, gu, gv):
         x, u0, v0 = ctx.saved_tensors
-        T, G, solver, eps = ctx.cfg
+        T, G, solver, eps, fam = ctx.cfg
         if G <= 0:
-            return torch.zeros_like(x), None, None, None, None, None, None
-        gx = _gnmf_bwd_raw(x, u0, v0, None, gu.contiguous(), gv.contiguous(), T, G, solver, eps)
-        return gx, None, None, None, None, None, None
+            return (torch.zeros_like(x), *[None] * 7)
+        gx = _gnmf_bwd_raw(x, u0, v0, None, gu.contiguous(), gv.contiguous(), T, G, solver, eps, fam)
+        return (gx, *[None] * 7)
 
 
 def gnmf(x, u0, v0, T, G, solver, eps=1e-16):
-    return GNMFFn.apply(x, u0, v0, T, G, solver, eps)
+    return GNMFFn.apply(x, u0, v0, T, G, solver, eps, "gnmf")
 
 
 def gnmf_decompose(x, u0, v0, T, G, solver, eps=1e-16):
-    return GNMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps)
+    return GNMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps, "gnmf")
+
+
+def gnmfx(x, u0, v0, T, G, solver, eps=1e-16):
+    return GNMFFn.apply(x, u0, v0, T, G, solver, eps, "gnmfx")
+
+
+def gnmfx_decompose(x, u0, v0, T, G, solver, eps=1e-16):
+    return GNMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps, "gnmfx")
 
 
 # ---- fused FactMixer core on channels-first tensors ------------------------------------------

@@ -415,7 +415,8 @@ class MatrixFactorization(nn.Module):
     # -- which path -------------------------------------------------------------------
     def _native_solver(self, x: Tensor):
         """Solver id if this call is covered by the gfx950 kernels, else None; `self._wide` then says which
-        family: the wave-resident kernels (False) or the split-N kernels for wide matrices (True)."""
+        family: the wave-resident kernels (False) or a split-N family for wide matrices ("gnmf": M <= 64, rank <= 4;
+        "gnmfx": M <= 512, rank <= 32, MU / HALS)."""
         self._wide = False
         if not x.is_cuda or self.verbose or not x.numel():
             return None
@@ -431,10 +432,14 @@ class MatrixFactorization(nn.Module):
         G = min(max(self.num_grad_steps, 0), self.num_iters)
         if not Fn.nmf_supported(self.size[0], self.size[1], self.rank, self.num_iters, G):
             # wider than one wavefront can hold (global Matricize, num_heads= forms): the split-N kernels
-            if x.dtype == torch.float32 and Fn.gnmf_supported(self.size[0], self.size[1], self.rank, self.num_iters, G) \
-                    and x.numel() // (self.size[0] * self.size[1]) <= 65535:
-                self._wide = True
-                return sid
+            if x.dtype == torch.float32 and x.numel() // (self.size[0] * self.size[1]) <= 65535:
+                if Fn.gnmf_supported(self.size[0], self.size[1], self.rank, self.num_iters, G):
+                    self._wide = "gnmf"
+                    return sid
+                # ranks up to 32, up to 512 rows (rank=None of the default-constructed model): MU and HALS only
+                if sid in ("mu", "hals") and Fn.gnmfx_supported(self.size[0], self.size[1], self.rank, self.num_iters, G):
+                    self._wide = "gnmfx"
+                    return sid
             composed.warn_once(
                 f"nmf{self.size}{self.rank}",
                 f"NMF size={self.size} rank={self.rank} is outside the native kernel families; "
@@ -454,7 +459,7 @@ class MatrixFactorization(nn.Module):
         x = x.as_subclass(Tensor)
         sid = self._native_solver(x) if not args and not kwargs else None   # (extra solver arguments — wmu's weights — : composed)
         if sid is not None:
-            fn = Fn.gnmf_decompose if self._wide else Fn.nmf_decompose
+            fn = {False: Fn.nmf_decompose, "gnmf": Fn.gnmf_decompose, "gnmfx": Fn.gnmfx_decompose}[self._wide]
             return fn(x, self.init.u0, self.init.v0, self.num_iters,
                       min(max(self.num_grad_steps, 0), self.num_iters), sid, self.solver.eps)
         if x.dtype in (torch.bfloat16, torch.float16):
@@ -481,7 +486,7 @@ class MatrixFactorization(nn.Module):
         x = x.as_subclass(Tensor)
         sid = self._native_solver(x)
         if sid is not None:
-            fn = Fn.gnmf if self._wide else Fn.nmf
+            fn = {False: Fn.nmf, "gnmf": Fn.gnmf, "gnmfx": Fn.gnmfx}[self._wide]
             return fn(x, self.init.u0, self.init.v0, self.num_iters,
                       min(max(self.num_grad_steps, 0), self.num_iters), sid, self.solver.eps)
         u, v = self.decompose(x)

@@ -162,6 +162,25 @@ int fz_gnmf_bwd(const float* x, const float* u0, const float* v0, const float* g
                 const float* gv, float* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad, int solver,
                 float eps, void* workspace, fz_stream_t stream);
 
+/* ---- split-N NMF for ranks up to 32 and matrices up to 512 rows (csrc/nmf_global_rank.hip) -------------
+ * The reference's default-constructed model: Matricize(num_heads=1, grid_size=1) with rank=None, i.e.
+ * rank = ceil(M N / (10 (M + N))) (matrix_factorization.py:406-408), e.g. 64 x 262 144 R 7, 256 x 4 096 R 25,
+ * 512 x 512 R 26.  Same semantics and argument lists as fz_gnmf_fwd / fz_gnmf_bwd; fp32; solvers FZ_SOLVER_MU and
+ * FZ_SOLVER_HALS only (anything else is refused, FZ_E_ARG).  fz_gnmfx_supported: 16 <= M <= 512, 1 <= R <= min(32, M),
+ * N >= 1, T >= 0, and R > 4 or M > 64 (the shapes fz_gnmf_* takes are refused here); nmat <= 65535.  No float atomics,
+ * every cross-workgroup sum two-stage in a fixed order: results replay bit for bit and do not depend on the other
+ * matrices of the batch.  One call issues fz_gnmfx_launches(M, N, R, T, Tgrad, backward) kernels (3T forward, 1 for
+ * T = 0; 3T + 3G + 1 backward).  workspace: fz_gnmfx_workspace_bytes(...) bytes of device memory, caller-owned. */
+int fz_gnmfx_supported(int M, int64_t N, int R, int T, int Tgrad);
+int64_t fz_gnmfx_workspace_bytes(int64_t nmat, int M, int64_t N, int R, int T, int backward);
+int fz_gnmfx_launches(int M, int64_t N, int R, int T, int Tgrad, int backward);
+int fz_gnmfx_fwd(const float* x, const float* u0, const float* v0, float* y, float* u_out, float* v_out,
+                 int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, void* workspace,
+                 fz_stream_t stream);
+int fz_gnmfx_bwd(const float* x, const float* u0, const float* v0, const float* gy, const float* gu,
+                 const float* gv, float* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad, int solver,
+                 float eps, void* workspace, fz_stream_t stream);
+
 /* ---- FactMixer core on channels-first tensors (hot shape: head_dim 8, patch 8x8x8) -----------
  * One launch per shift window performs SWMatricize.forward → NMF.forward →
  * SWMatricize.inverse_forward (factorizer.py:41-50; operations.py:417-434;

@@ -182,6 +182,22 @@ class GemmDesc(_c.Structure):
                 ("lnb_gadd", _vp), ("lnb_part", _vp), ("act_dtype", _i), ("products", _i), ("tune", _i)]
 
 
+class OutprojFac(_c.Structure):
+    """fz_outproj_fac (include/factorizer_hip.h): the core's output as the rank-1 factors of its two windows, for
+    fz_mlp_chain_fac / fz_gemm_dw_fac"""
+    _fields_ = [("v", _vp * 2), ("u", _vp * 2), ("dims", _i * 3), ("heads", _i), ("shift", _i * 6)]
+
+
+def outproj_fac(fac, geo):
+    """fz_outproj_fac of fac = (vfac0, ufac0, vfac1, ufac1) (functional.core_factors) on geometry `geo`"""
+    d = OutprojFac()
+    d.v[0], d.u[0], d.v[1], d.u[1] = (t.data_ptr() for t in fac)
+    d.dims[:] = list(geo.spatial)
+    d.heads = geo.h
+    d.shift[:] = [int(v) for s in geo.shifts3 for v in s]
+    return d
+
+
 class MlpDesc(_c.Structure):
     _fields_ = [("mode", _i), ("inp", _vp), ("w1", _vp), ("w2", _vp), ("b1", _vp), ("b2", _vp), ("ln_g", _vp),
                 ("ln_b", _vp), ("ln_eps", _f), ("stats", _vp), ("z1", _vp), ("gz1", _vp), ("x1", _vp), ("out", _vp),
@@ -249,6 +265,8 @@ _SIGS.update({
     "fz_nmf_cf_fwd": ([_vp] * 4 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 5 + [_f, _i, _vp], _i),
     "fz_nmf_cf_bwd": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 7 + [_f, _i, _vp], _i),
     "fz_nmf_cf_factors_supported": ([_i] * 12 + [_c.POINTER(_i)], _i),
+    "fz_nmf_cf_factors_to_tensor": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] * 2 + [_i, _vp], _i),
+    "fz_outproj_factors_supported": ([_i] * 13 + [_c.POINTER(_i)] + [_i] * 3, _i),
     "fz_nmf_cf_fwd_store_factors": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 3 + [_f, _i, _vp], _i),
     "fz_nmf_cf_fwd_from_factors": ([_vp] * 6 + [_i] * 5 + [_c.POINTER(_i)] * 2 + [_i] * 4 + [_f, _i, _vp], _i),
     "fz_nmf_cf_bwd_factors_supported": ([_i] * 14 + [_c.POINTER(_i)], _i),
@@ -262,6 +280,8 @@ _SIGS.update({
     "fz_mlp_pre_supported": ([_i, _i, _i64, _i], _i),
     "fz_mlp_drop_supported": ([_i, _i, _i64, _i], _i),
     "fz_mlp_chain_drop": ([_c.POINTER(MlpDesc), _c.POINTER(MlpDropout), _vp], _i),
+    "fz_mlp_chain_fac": ([_c.POINTER(MlpDesc), _c.POINTER(OutprojFac), _vp], _i),
+    "fz_gemm_dw_fac": ([_c.POINTER(GemmDwDesc), _c.POINTER(OutprojFac), _vp], _i),
     "fz_conv3_prologue_supported": ([_i] * 4, _i),
     "fz_conv3_fwd2": ([_vp] * 4 + [_i] * 8 + [_c.POINTER(BlockPrologue), _vp], _i),
     "fz_upcat2": ([_vp, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_c.POINTER(BlockPrologue), _vp], _i),

@@ -3,6 +3,7 @@
 #include "gemm_bx.h"       // split-bf16 operand helpers (brings gemm_common.h)
 #include "gemm_shared.h"   // half_sum32, DropArgs, kTS, knob_pos
 #include "finish.h"        // kDwRow and the job that adds the weight-gradient rows
+#include "outproj_fac.h"   // FacArgs, fac_fetch, fac_build: the core's output as the factors of its two windows
 
 namespace fz {
 
@@ -14,6 +15,9 @@ namespace fz {
 // MFMA operands of dW come straight from memory in [channel][voxel] order, so each wave parks its g tile and its q
 // tile in LDS (stride kTS) and reads them back with the channel on the lane axis — no register transposes.
 // Persistent workgroups (two per CU), sums carried in registers across tiles, one wpart row per workgroup.
+// FAC (a trailing FacArgs; out_proj, fp32 storage): q is the core's output a, which is not stored — the wave rebuilds its q tile
+// from the rank-1 factors of the core's two windows (outproj_fac.h), fetched one tile ahead beside g and staged through the
+// wave's Qb rows before the rebuilt rows are written there.
 // =================================================================================================
 // (kDwRow — floats of one wpart row: dW [32][32] | db [32] | dγ [32] | dβ [32] (LNB) — lives in finish.h)
 
@@ -34,8 +38,12 @@ struct DwArgsT {
 
 template <bool LNB, typename AT, typename... DropX>
 __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(DwArgsT<AT> p, int ntiles, DropX... dx) {
-  constexpr bool DROP = sizeof...(DropX) > 0;   // the block-dropout form (one trailing DropArgs): g is read as M0 s0 g
+  constexpr bool FAC = is_fac_v<DropX...>;      // the factor form: one trailing FacArgs
+  constexpr bool DROP = sizeof...(DropX) > 0 && !FAC;   // the block-dropout form (one trailing DropArgs): g is read as M0 s0 g
   const DropArgs dr = drop_of(dx...);
+  const FacArgs fa = fac_of(dx...);
+  static_assert(!FAC || (!LNB && sizeof(AT) == 4), "factors: the out-projection pair, fp32 storage");
+  static_assert(kFacLds <= 32 * kTS, "the factor staging area lives in the wave's Qb rows");
   constexpr int NACC = 2;
   constexpr int kWave = 64 * kTS;             // floats of one wave's (Gb | Qb) region
   // BXB (bf16 storage): both GEMMs on the bf16 matrix pipe with fp32-accurate products — the activations are exact bf16
@@ -89,9 +97,14 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(DwArgsT<AT> p, int ntil
 
   int tile = blockIdx.x;
   float bv[16][NACC];
+  FacTile ft;   // (FAC) the factors of the NEXT / current q tile
   auto fetch_tile = [&](int t) {
     const int bt = t / tiles_per_sample;
     const int64_t ct = ((int64_t)(t % tiles_per_sample) * 4 + wave) * (32 * NACC) + NACC * j;
+    if constexpr (FAC) {
+      const int64_t n0 = ((int64_t)(t % tiles_per_sample) * 4 + wave) * (32 * NACC);
+      fac_fetch(fa, bt, (unsigned)(n0 < p.V ? n0 : 0), lane, ft);
+    }
     const unsigned lo = (unsigned)h * (unsigned)p.V + (unsigned)(ct < p.V ? ct : 0);
     const AT* xb = p.g + (int64_t)bt * 32 * p.V;
 #pragma unroll
@@ -125,6 +138,13 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(DwArgsT<AT> p, int ntil
       vload<NACC>(sp + nc, mu);
       vload<NACC>(sp + p.V + nc, rs);
     }
+    if constexpr (FAC) {
+      float qv[16][NACC];
+      fac_build(fa, ft, Qb, lane, qv);
+#pragma unroll
+      for (int s = 0; s < 16; ++s)
+        *reinterpret_cast<float2*>(Qb + (2 * s + h) * kTS + 2 * j) = make_float2(col_ok ? qv[s][0] : 0.f, col_ok ? qv[s][1] : 0.f);
+    } else
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       float xv[8][NACC];
@@ -344,7 +364,7 @@ static int knob_gemm_dw_wgs() { return knob_pos(FZ_KNOB("FZ_GEMM_DW_WGS"), 512);
 
 extern "C" int fz_gemm_dw_rows(int B, int64_t V);
 template <typename AT>
-static int gemm_dw_launch(const fz_gemm_dw_desc* d, fz_stream_t stream) {
+static int gemm_dw_launch(const fz_gemm_dw_desc* d, const fz_outproj_fac* fac, fz_stream_t stream) {
   DwArgsT<AT> a;
   a.g = (const AT*)d->g; a.q = (const AT*)d->q; a.w = d->w; a.ldw = d->ldw > 0 ? d->ldw : 32; a.stats = d->stats; a.ln_g = d->ln_g; a.gadd = (const AT*)d->gadd;
   a.y = (AT*)d->y; a.wpart = (float*)d->wpart; a.V = d->V; a.B = d->B;
@@ -352,7 +372,18 @@ static int gemm_dw_launch(const fz_gemm_dw_desc* d, fz_stream_t stream) {
   const int rows = fz_gemm_dw_rows(d->B, d->V);
   constexpr int lds = (1536 + 32 + 256 + 4 * 64 * kTS) * (int)sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (d->drop_m) {   // site 0 on g (out_proj: no LayerNorm form)
+  if (fac) {   // (gemm_dw_entry has refused the factor form with ln, dropout or bf16 storage)
+    if constexpr (sizeof(AT) == 4) {
+      FacArgs fa;
+      const int rc = fac_args(fac, d->V, "fz_gemm_dw_fac", fa);
+      if (rc != FZ_OK) return rc;
+      auto kern = gemm_dw_kernel<false, AT, FacArgs>;
+      FZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(256), lds, st, a, ntiles, fa);
+    } else {
+      return fail(FZ_E_UNSUPPORTED, "fz_gemm_dw_fac: fp32 storage only");
+    }
+  } else if (d->drop_m) {   // site 0 on g (out_proj: no LayerNorm form)
     auto kern = gemm_dw_kernel<false, AT, DropArgs>;
     FZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(256), lds, st, a, ntiles, drop_args(d->drop_m, nullptr, nullptr, d->drop_s, 1.f, 1.f, d->V));
@@ -381,9 +412,12 @@ extern "C" int64_t fz_gemm_dw_workspace_bytes(int B, int64_t V) {
   return (int64_t)fz_gemm_dw_rows(B, V) * kDwRow * (int64_t)sizeof(float);
 }
 
-extern "C" int fz_gemm_dw(const fz_gemm_dw_desc* d, fz_stream_t stream) {
+// fac (fz_gemm_dw_fac): q as the rank-1 factors of the core's two windows, q itself null
+static int gemm_dw_entry(const fz_gemm_dw_desc* d, const fz_outproj_fac* fac, fz_stream_t stream) {
   if (!d) return fail(FZ_E_ARG, "fz_gemm_dw: null descriptor");
-  if (!d->g || !d->q || !d->w || !d->y || !d->wpart || !d->gw) return fail(FZ_E_ARG, "fz_gemm_dw: null pointer");
+  if (fac && (d->q || d->ln || d->drop_m || d->act_dtype != FZ_STORE_F32 || d->C != 32))
+    return fail(FZ_E_UNSUPPORTED, "fz_gemm_dw_fac: needs q == NULL, no LayerNorm form, no dropout, fp32 storage, C == 32 (fz_outproj_factors_supported)");
+  if (!d->g || (!d->q && !fac) || !d->w || !d->y || !d->wpart || !d->gw) return fail(FZ_E_ARG, "fz_gemm_dw: null pointer");
   if (d->ln && (!d->stats || !d->ln_g || !d->ln_b || !d->gln)) return fail(FZ_E_ARG, "fz_gemm_dw: the LayerNorm form needs stats, gamma, beta, gln");
   if (!d->ln && d->gadd) return fail(FZ_E_UNSUPPORTED, "fz_gemm_dw: gadd only with the LayerNorm backward");
   if (d->drop_m && d->ln) return fail(FZ_E_UNSUPPORTED, "fz_gemm_dw: dropout on g only without the LayerNorm backward");
@@ -392,7 +426,14 @@ extern "C" int fz_gemm_dw(const fz_gemm_dw_desc* d, fz_stream_t stream) {
   if (d->ldgw != 0 && d->ldgw < 32) return fail(FZ_E_ARG, "fz_gemm_dw: ldgw must be 0 (= 32) or >= 32");
   if (d->ldw != 0 && d->ldw < 32) return fail(FZ_E_ARG, "fz_gemm_dw: ldw must be 0 (= 32) or >= 32");
   if (d->B < 1 || d->V < 1 || d->V % 4 != 0 || d->V > ((int64_t)1 << 27)) return fail(FZ_E_UNSUPPORTED, "fz_gemm_dw: needs B >= 1, V % 4 == 0, V <= 2^27");
-  if (d->act_dtype == FZ_STORE_F32) return gemm_dw_launch<float>(d, stream);
-  if (d->act_dtype == FZ_STORE_BF16) return gemm_dw_launch<bf16>(d, stream);
+  if (d->act_dtype == FZ_STORE_F32) return gemm_dw_launch<float>(d, fac, stream);
+  if (d->act_dtype == FZ_STORE_BF16) return gemm_dw_launch<bf16>(d, fac, stream);
   return fail(FZ_E_ARG, "fz_gemm_dw: act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
+}
+
+extern "C" int fz_gemm_dw(const fz_gemm_dw_desc* d, fz_stream_t stream) { return gemm_dw_entry(d, nullptr, stream); }
+
+extern "C" int fz_gemm_dw_fac(const fz_gemm_dw_desc* d, const fz_outproj_fac* fac, fz_stream_t stream) {
+  if (!fac) return fail(FZ_E_ARG, "fz_gemm_dw_fac: null factor block");
+  return gemm_dw_entry(d, fac, stream);
 }

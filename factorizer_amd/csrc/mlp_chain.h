@@ -64,9 +64,11 @@ static int knob_chain_fwd_bx() { const auto& k = FZ_KNOB("FZ_CHAIN_FWD_BX"); ret
 static int knob_mlp_wgs(int dflt) { return knob_pos(FZ_KNOB("FZ_MLP_WGS"), dflt); }
 
 // ---- the launchers: fz_mlp_chain's dispatcher (mlp_chain.hip) has checked the descriptor and filled the argument blocks ----
-// C = 32, modes 0 and 1: gemm_chain_kernel (mlp_chain32.hip); `drop` is null unless a dropout plane is live
+// C = 32, modes 0 and 1: gemm_chain_kernel (mlp_chain32.hip); `drop` is null unless a dropout plane is live, `fac` unless the
+// out-projection's operand comes as the core's factors (fz_mlp_chain_fac)
 template <typename AT>
-int chain32_launch(const fz_mlp_desc* d, const fz_mlp_dropout* drop, const GemmArgsT<AT>& a, const ChainArgsT<AT>& c, fz_stream_t stream);
+int chain32_launch(const fz_mlp_desc* d, const fz_mlp_dropout* drop, const fz_outproj_fac* fac, const GemmArgsT<AT>& a, const ChainArgsT<AT>& c,
+                   fz_stream_t stream);
 // C = 64, modes 0 and 1: gemm_chain64_kernel (mlp_chain64.hip)
 template <typename AT>
 int chain64_launch(const fz_mlp_desc* d, const GemmArgsT<AT>& a, const ChainArgsT<AT>& c, fz_stream_t stream);

@@ -23,6 +23,15 @@ extern "C" int fz_mlp_pre_supported(int C, int H, int64_t V, int products) {
   return 0;
 }
 
+// where both consumers of the core's output a at C = 32 — this chain's GEMM 0 and fz_gemm_dw's q operand — rebuild a from the
+// factors of the core's two windows (outproj_fac.h) and a is never stored
+extern "C" int fz_outproj_factors_supported(int C, int Hd, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
+                                            int nshift, const int* shifts, int act_dtype, int products, int dropout) {
+  if (C != 32 || Hd != 64 || act_dtype != FZ_STORE_F32 || dropout || nshift != 2) return 0;
+  if (!fz_nmf_cf_factors_supported(C, D, H, W, d, pd, ph, pw, R, T, Tgrad, nshift, shifts)) return 0;
+  return fz_mlp_pre_supported(C, Hd, (int64_t)D * H * W, products);   // split-bf16 products, V <= 2^27 (fz_gemm_dw's bound too)
+}
+
 extern "C" int fz_mlp_supported(int C, int H, int64_t V) {
   const bool shape = (C == 32 && (H == 64 || H == 128)) || (C == 64 && H == 128);
   return (shape && V > 0 && (V % 4) == 0 && V <= ((int64_t)1 << 27)) ? 1 : 0;
@@ -36,12 +45,12 @@ extern "C" int fz_mlp_drop_supported(int C, int H, int64_t V, int products) {
 // The argument blocks of the chain (GemmArgsT: GEMM 1 and the epilogue; ChainArgsT: GEMM 2 and the fused neighbours).
 // forward: A1[m][k] = W1[m][k] behind the LayerNorm, A2[m][k] = W2[m][k]; z1 goes to `side`
 template <typename AT>
-static void forward_args(const fz_mlp_desc* d, int ldw, int ldwB, GemmArgsT<AT>& a, ChainArgsT<AT>& c) {
+static void forward_args(const fz_mlp_desc* d, bool fac, int ldw, int ldwB, GemmArgsT<AT>& a, ChainArgsT<AT>& c) {
   a.w = d->w1; a.w_t = 0; a.ldw = ldw;
   a.bias = d->b1; a.ln = 1; a.ln_g = d->ln_g; a.ln_b = d->ln_b; a.ln_eps = d->ln_eps; a.stats_out = d->stats;
   a.res = (const AT*)d->in; a.y = (AT*)d->out;
   c.wB = d->w2; c.wB_t = 0; c.ldwB = ldwB; c.biasB = d->b2; c.side = (AT*)d->z1;
-  if (d->pre_in) {   // the block's out-projection in front of the chain (x1 is then an OUTPUT), at C = 32 the head behind it
+  if (d->pre_in || fac) {   // the block's out-projection in front of the chain (x1 is then an OUTPUT), at C = 32 the head behind it; fac: pre_in stays null
     c.preA = (const AT*)d->pre_in; c.preW = d->pre_w; c.preB = d->pre_b; c.preRes = (const AT*)d->pre_res; c.preOut = (AT*)d->pre_out;
     if (d->C == 64) a.res = (const AT*)d->pre_out;   // the epilogue's residual: the lane's own x1, written a moment earlier
     else { c.postW = d->post_w; c.postB = d->post_b; c.postOut = (AT*)d->post_out; c.postM = d->post_m; }
@@ -57,7 +66,7 @@ static void backward_args(const fz_mlp_desc* d, int ldw, int ldwB, AT* side, Gem
 }
 
 // what fz_mlp_chain refuses, in the order its callers see it
-static int mlp_check(const fz_mlp_desc* d, const fz_mlp_dropout* dd, bool drop) {
+static int mlp_check(const fz_mlp_desc* d, const fz_mlp_dropout* dd, bool drop, bool fac) {
   if (!fz_mlp_supported(d->C, d->H, d->V)) return fail(FZ_E_UNSUPPORTED, "fz_mlp_chain: needs (C, H) in {(32, 64), (32, 128), (64, 128)}, V % 4 == 0");
   if (drop) {
     if (!fz_mlp_drop_supported(d->C, d->H, d->V, d->products) || d->mode != 0 || !d->pre_in)
@@ -67,7 +76,12 @@ static int mlp_check(const fz_mlp_desc* d, const fz_mlp_dropout* dd, bool drop) 
   }
   if (d->C == 64 && d->mode == 2) return fail(FZ_E_UNSUPPORTED, "fz_mlp_chain: the fused weight gradients need C == 32, H == 64");
   if (d->B < 0) return fail(FZ_E_SHAPE, "fz_mlp_chain: negative batch");
-  const bool pre = d->pre_in != nullptr;   // the block's out-projection in front of the forward chain (x1 is then an OUTPUT)
+  // the factor form of pre_in (fz_mlp_chain_fac: the core's output as the rank-1 factors of its two windows) exists for one
+  // kernel; every other launch that brings factors is refused, never run on a tensor that is not there
+  if (fac && (d->C != 32 || d->H != 64 || d->mode != 0 || d->act_dtype != FZ_STORE_F32 || drop || d->pre_in
+              || !fz_mlp_pre_supported(d->C, d->H, d->V, d->products)))
+    return fail(FZ_E_UNSUPPORTED, "fz_mlp_chain_fac: needs (C, H) = (32, 64), mode 0, fp32 storage, split-bf16 products, pre_in == NULL (fz_outproj_factors_supported)");
+  const bool pre = d->pre_in != nullptr || fac;   // the block's out-projection in front of the forward chain (x1 is then an OUTPUT)
   if (pre && (d->mode != 0 || !d->pre_w || !d->pre_res || !d->pre_out))
     return fail(FZ_E_ARG, "fz_mlp_chain: pre_in needs mode 0, pre_w, pre_res, pre_out (see fz_mlp_pre_supported)");
   if (pre && !fz_mlp_pre_supported(d->C, d->H, d->V, d->products))
@@ -86,9 +100,9 @@ static int mlp_check(const fz_mlp_desc* d, const fz_mlp_dropout* dd, bool drop) 
 }
 
 template <typename AT>
-static int mlp_launch(const fz_mlp_desc* d, const fz_mlp_dropout* dd, fz_stream_t stream) {
+static int mlp_launch(const fz_mlp_desc* d, const fz_mlp_dropout* dd, const fz_outproj_fac* fac, fz_stream_t stream) {
   const bool drop = dd && (dd->m0 || dd->m1 || dd->m2);   // block dropout: the DROP form of mode 0 with pre_in
-  const int rc = mlp_check(d, dd, drop);
+  const int rc = mlp_check(d, dd, drop, fac != nullptr);
   if (rc != FZ_OK) return rc;
   if (d->B == 0) {
     if (d->mode == 2) {   // no voxels: the sums are empty
@@ -104,23 +118,30 @@ static int mlp_launch(const fz_mlp_desc* d, const fz_mlp_dropout* dd, fz_stream_
   GemmArgsT<AT> a = {};
   ChainArgsT<AT> c = {};
   a.x[0] = (const AT*)d->in; a.nsrc = 1; a.c0 = d->C; a.Cin = d->C; a.Vin = d->V; a.M = d->H; a.K = d->C; a.Ncol = d->V; a.B = d->B;
-  if (d->mode == 0) forward_args(d, d->C, d->H, a, c);
+  if (d->mode == 0) forward_args(d, fac != nullptr, d->C, d->H, a, c);
   else backward_args(d, d->H, d->C, d->mode == 1 ? (AT*)d->gz1 : (AT*)nullptr, a, c);   // (mode 2 keeps gz1 on chip)
   if (d->C == 64) return chain64_launch(d, a, c, stream);
   if (d->mode == 2) return chain_wg_launch(d, a, c, stream);
-  return chain32_launch(d, drop ? dd : nullptr, a, c, stream);
+  return chain32_launch(d, drop ? dd : nullptr, fac, a, c, stream);
 }
 
 extern "C" int fz_mlp_chain(const fz_mlp_desc* d, fz_stream_t stream) {
   if (!d) return fail(FZ_E_ARG, "fz_mlp_chain: null descriptor");
-  if (d->act_dtype == FZ_STORE_F32) return mlp_launch<float>(d, nullptr, stream);
-  if (d->act_dtype == FZ_STORE_BF16) return mlp_launch<bf16>(d, nullptr, stream);
+  if (d->act_dtype == FZ_STORE_F32) return mlp_launch<float>(d, nullptr, nullptr, stream);
+  if (d->act_dtype == FZ_STORE_BF16) return mlp_launch<bf16>(d, nullptr, nullptr, stream);
   return fail(FZ_E_ARG, "fz_mlp_chain: act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
+}
+
+extern "C" int fz_mlp_chain_fac(const fz_mlp_desc* d, const fz_outproj_fac* fac, fz_stream_t stream) {
+  if (!d || !fac) return fail(FZ_E_ARG, "fz_mlp_chain_fac: null descriptor");
+  if (d->act_dtype == FZ_STORE_F32) return mlp_launch<float>(d, nullptr, fac, stream);
+  if (d->act_dtype == FZ_STORE_BF16) return mlp_launch<bf16>(d, nullptr, fac, stream);   // (refused by the checks: fp32 storage only)
+  return fail(FZ_E_ARG, "fz_mlp_chain_fac: act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
 }
 
 extern "C" int fz_mlp_chain_drop(const fz_mlp_desc* d, const fz_mlp_dropout* drop, fz_stream_t stream) {
   if (!d || !drop) return fail(FZ_E_ARG, "fz_mlp_chain_drop: null descriptor");
-  if (d->act_dtype == FZ_STORE_F32) return mlp_launch<float>(d, drop, stream);
-  if (d->act_dtype == FZ_STORE_BF16) return mlp_launch<bf16>(d, drop, stream);
+  if (d->act_dtype == FZ_STORE_F32) return mlp_launch<float>(d, drop, nullptr, stream);
+  if (d->act_dtype == FZ_STORE_BF16) return mlp_launch<bf16>(d, drop, nullptr, stream);
   return fail(FZ_E_ARG, "fz_mlp_chain_drop: act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
 }

@@ -1,6 +1,7 @@
 // mlp_chain32.hip — the chained MLP of the C = 32 blocks on the matrix cores (gemm.hip has the MFMA mapping it shares):
 // gemm_chain_kernel and its host launcher, reached from fz_mlp_chain's dispatcher (mlp_chain.hip).
 #include "mlp_chain.h"     // ChainArgsT, chain_stagger, knob_mlp_wgs, knob_chain_fwd_bx, chain32_launch
+#include "outproj_fac.h"   // FacArgs, fac_fetch, fac_build: the core's output as the factors of its two windows
 
 namespace fz {
 
@@ -27,12 +28,19 @@ namespace fz {
 // pre-split in LDS as bf16x8 triples (12 KB per GEMM at HB = 2 instead of 8: two workgroups per CU instead of three).  Why: an fp32
 // MFMA blocks the SIMD's vector issue for its whole duration — the 128 fp32 MFMAs of a tile were 48 % of this
 // kernel's time with nothing running beside them — a bf16 MFMA for a quarter of its own.
+// FAC (a trailing FacArgs, with PRE, fp32 storage): the core's output a is not a tensor — GEMM 0's operand tile is rebuilt from
+// the rank-1 factors of the core's two windows (outproj_fac.h), fetched one tile ahead like the tile of a they replace and
+// staged through the wave's stash rows, which are free until GEMM 0's epilogue writes x1 there.
 // (Six-wave workgroups — 73 KB, two per CU, three waves per SIMD again — were tried and are slower than these four-wave ones at two
 // waves per SIMD: 1.06 against 0.97 ms per step for the two launches, fp32 form 1.09; profiles/r04_chain_fwd_bx_ab.log.)
 template <bool BWD, int NACC, int HB, typename AT = float, bool BX = false, bool PRE = false, typename... DropX>
 __global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2) void gemm_chain_kernel(GemmArgsT<AT> p, ChainArgsT<AT> c, int ntiles, DropX... dx) {
-  constexpr bool DROP = sizeof...(DropX) > 0;   // the block-dropout form: one trailing DropArgs (the p = 0 kernels have no such argument)
+  constexpr bool FAC = is_fac_v<DropX...>;      // the factor form: one trailing FacArgs
+  constexpr bool DROP = sizeof...(DropX) > 0 && !FAC;   // the block-dropout form: one trailing DropArgs (the p = 0 kernels have no such argument)
   const DropArgs dr = drop_of(dx...);
+  const FacArgs fa = fac_of(dx...);
+  static_assert(!FAC || (PRE && !BWD && NACC == 2 && sizeof(AT) == 4), "factors: the forward chain with the out-projection in front, fp32 storage");
+  static_assert(kFacLds <= 32 * 32 * NACC, "the factor staging area lives in the wave's stash rows");
   static_assert(!DROP || (PRE && !BWD && NACC == 2), "dropout: the forward chain with the out-projection in front");
   constexpr int NW = 4;
   constexpr int HID = 32 * HB, N1 = BX ? 1536 * HB : 16 * HB * 64;  // hidden rows; floats of each staged weight block
@@ -144,14 +152,20 @@ __global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2)
   int tile = blockIdx.x;
   float bv[16][NACC];
   float xr[PRE ? 16 : 1][NACC];   // (PRE) residual rows of the NEXT / current tile
+  FacTile ft;                     // (FAC) the factors of the NEXT / current tile
   // operand loads: channel 2s + h → uniform part (b*32 + 2s)*V in scalar registers + ONE lane offset
   auto fetch_tile = [&](int t) {
     const int bt = t / tiles_per_sample;
     const int64_t ct = ((int64_t)(t % tiles_per_sample) * NW + wave) * (32 * NACC) + NACC * j;
     const unsigned lo = (unsigned)h * (unsigned)p.Ncol + (unsigned)(ct < p.Ncol ? ct : 0);
+    if constexpr (FAC) {
+      const int64_t n0 = ((int64_t)(t % tiles_per_sample) * NW + wave) * (32 * NACC);
+      fac_fetch(fa, bt, (unsigned)(n0 < p.Ncol ? n0 : 0), lane, ft);
+    } else {
     const AT* xb = (PRE ? c.preA : p.x[0]) + (int64_t)bt * 32 * p.Ncol;
 #pragma unroll
     for (int s = 0; s < 16; ++s) vload<NACC>(xb + (int64_t)(2 * s) * p.Ncol + lo, bv[s]);
+    }
     if constexpr (PRE) {   // the residual rows of x in the accumulator layout (row (r & 3) + 8 (r >> 2) + 4h)
       const unsigned lr = (unsigned)(4 * h) * (unsigned)p.Ncol + (unsigned)(ct < p.Ncol ? ct : 0);
       const AT* rb0 = c.preRes + (int64_t)bt * 32 * p.Ncol;
@@ -175,6 +189,7 @@ __global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2)
       // ---- GEMM 0: x1 = W_o a + b_o + x on the accumulators; x1 -> HBM (for the backward) and -> stash (the chain's residual);
       //      bv becomes x̂ in the ACCUMULATOR layout (register r = row (r & 3) + 8 (r >> 2) + 4h) — GEMM 1's weights are staged
       //      in that order ----
+      if constexpr (FAC) fac_build(fa, ft, &stash[wave][0][0], lane, bv);
       f32x16 acc0[NACC];
 #pragma unroll
       for (int q = 0; q < NACC; ++q)
@@ -435,10 +450,11 @@ __global__ __launch_bounds__(256, (NACC == 2 && HB == 2 && !BWD && !BX) ? 3 : 2)
 // Replaces, per FactorizerBlock, Linear∘LayerNorm + Linear∘GELU + residual (layers/mlp.py:54-63, factorizer.py:76) in the
 // forward and the two input-gradient GEMMs + LayerNorm backward in the backward.
 template <typename AT>
-int chain32_launch(const fz_mlp_desc* d, const fz_mlp_dropout* drop, const GemmArgsT<AT>& a, const ChainArgsT<AT>& c, fz_stream_t stream) {
+int chain32_launch(const fz_mlp_desc* d, const fz_mlp_dropout* drop, const fz_outproj_fac* fac, const GemmArgsT<AT>& a, const ChainArgsT<AT>& c,
+                   fz_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
   const int ntiles = (int)fz_mlp_partials(d->B, d->V);
-  const bool bwd = d->mode != 0, pre = d->pre_in != nullptr;
+  const bool bwd = d->mode != 0, pre = d->pre_in != nullptr || fac;   // (fac: the out-projection's operand as the core's factors)
   // forward at hidden 64 on split-bf16 products (FZ_CHAIN_FWD_BX=0 in a probe build: the fp32-MFMA forward chain)
   const bool bx = !bwd && d->H == 64 && products_split(d->products) && knob_chain_fwd_bx();
   // resident workgroups, each walking tiles with a stride of the grid: three per CU for the fp32-MFMA forms at hidden 64,
@@ -451,6 +467,16 @@ int chain32_launch(const fz_mlp_desc* d, const fz_mlp_dropout* drop, const GemmA
   } else if (d->H == 128) hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 4>), grid, block, 0, st, a, c, ntiles);
   else if (!bx) hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 2>), grid, block, 0, st, a, c, ntiles);
   else if (!pre) hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 2, AT, true>), grid, block, 0, st, a, c, ntiles);
+  else if (fac) {   // (mlp_check has refused the factor form outside fp32 storage, hidden 64, split-bf16 products, no dropout)
+    if constexpr (sizeof(AT) == 4) {
+      FacArgs fa;
+      const int rc = fac_args(fac, d->V, "fz_mlp_chain_fac", fa);
+      if (rc != FZ_OK) return rc;
+      hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 2, AT, true, true, FacArgs>), grid, block, 0, st, a, c, ntiles, fa);
+    } else {
+      return fail(FZ_E_UNSUPPORTED, "fz_mlp_chain_fac: fp32 storage only");
+    }
+  }
   else if (!drop) hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 2, AT, true, true>), grid, block, 0, st, a, c, ntiles);
   else
     hipLaunchKernelGGL((gemm_chain_kernel<false, 2, 2, AT, true, true, DropArgs>), grid, block, 0, st, a, c, ntiles,
@@ -458,7 +484,7 @@ int chain32_launch(const fz_mlp_desc* d, const fz_mlp_dropout* drop, const GemmA
   FZ_LAUNCH_CHECK();
   return FZ_OK;
 }
-template int chain32_launch<float>(const fz_mlp_desc*, const fz_mlp_dropout*, const GemmArgsT<float>&, const ChainArgsT<float>&, fz_stream_t);
-template int chain32_launch<bf16>(const fz_mlp_desc*, const fz_mlp_dropout*, const GemmArgsT<bf16>&, const ChainArgsT<bf16>&, fz_stream_t);
+template int chain32_launch<float>(const fz_mlp_desc*, const fz_mlp_dropout*, const fz_outproj_fac*, const GemmArgsT<float>&, const ChainArgsT<float>&, fz_stream_t);
+template int chain32_launch<bf16>(const fz_mlp_desc*, const fz_mlp_dropout*, const fz_outproj_fac*, const GemmArgsT<bf16>&, const ChainArgsT<bf16>&, fz_stream_t);
 
 }  // namespace fz

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdlib>
 
+#include "cf_patch.h"   // cf_voxel_patch, cf_two_window_value: what the consumers of a factor pair share with this family
 #include "fz_common.h"
 #include "nmf_core.h"
 #include "nmf_gram.h"
@@ -345,6 +346,9 @@ struct CfLaunch {
 template <typename AT>
 int cf_fwd_launch(const AT* t, const float* u0, const float* v0, AT* out, float* vfac, float* ufac, const CfLaunch& a, int form,
                   int R, int T, int solver, float eps);
+// the averaged output of a two-window rank-1 forward from the factors both windows stored (nmf_cf_fwd.hip), fp32: a.q.s* =
+// window 0's shift, a.q.ps* = window 1's
+int cf_factors_to_tensor_launch(const float* vf0, const float* uf0, const float* vf1, const float* uf1, float* out, const CfLaunch& a);
 // one window of the backward (nmf_cf_bwd.hip): the row-space kernel where it applies and wins, else the general kernels
 template <typename AT>
 int cf_bwd_launch(const AT* t, const float* u0, const float* v0, const AT* ga, AT* gt, const CfLaunch& a, int relu_gate, int R,

@@ -160,6 +160,25 @@ extern "C" int fz_nmf_cf_fwd_from_factors(const void* t, const float* u0, const 
                         "fz_nmf_cf_fwd_from_factors: bad act_dtype");
 }
 
+// the tensor of a forward whose two windows BOTH left their factors (two fz_nmf_cf_fwd_store_factors launches): the bits of
+// fz_nmf_cf_fwd_store_factors + fz_nmf_cf_fwd_from_factors with divisor 2
+extern "C" int fz_nmf_cf_factors_to_tensor(const float* vfac0, const float* ufac0, const float* vfac1, const float* ufac1, void* out,
+                                           int B, int C, int D, int H, int W, const int* shift0, const int* shift1, int act_dtype,
+                                           fz_stream_t stream) {
+  if (act_dtype == FZ_STORE_BF16) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_factors_to_tensor: fp32 storage only");
+  if (act_dtype != FZ_STORE_F32) return fail(FZ_E_ARG, "fz_nmf_cf_factors_to_tensor: bad act_dtype");
+  CfLaunch a;
+  const int rc = cf_prepare(a, B, C, D, H, W, shift0, shift1, 0, 2, stream, [&](const CfGeom& q) {
+    if (!vfac0 || !ufac0 || !vfac1 || !ufac1 || !out || !shift1)
+      return fail(FZ_E_ARG, "fz_nmf_cf_factors_to_tensor: null pointer (vfac0, ufac0, vfac1, ufac1, out or shift1)");
+    if (W % 64) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_factors_to_tensor: W must be a multiple of 64");
+    if ((q.s2 % 4) || (q.ps2 % 4)) return fail(FZ_E_UNSUPPORTED, "fz_nmf_cf_factors_to_tensor: W-axis shift must be a multiple of 4");
+    return (int)FZ_OK;
+  });
+  if (rc != FZ_OK || a.nmat == 0) return rc;
+  return cf_factors_to_tensor_launch(vfac0, ufac0, vfac1, ufac1, (float*)out, a);
+}
+
 // ---- a two-window HALS rank-1 backward behind the ReLU that keeps the first window's gradient as its factors --------
 extern "C" int fz_nmf_cf_bwd_factors_supported(int C, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
                                                int solver, int relu_gate, int nshift, const int* shifts) {

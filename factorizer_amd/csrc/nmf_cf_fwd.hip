@@ -226,4 +226,41 @@ int cf_fwd_launch(const AT* t, const float* u0, const float* v0, AT* out, float*
 template int cf_fwd_launch<float>(const float*, const float*, const float*, float*, float*, float*, const CfLaunch&, int, int, int, int, float);
 template int cf_fwd_launch<bf16>(const bf16*, const float*, const float*, bf16*, float*, float*, const CfLaunch&, int, int, int, int, float);
 
+// a = ((0 + u0 v0ᵀ) + u1 v1ᵀ) / 2 from the factors of BOTH windows (two CF_STORE_FACTORS launches), in one pass: what the
+// out-projection's kernels rebuild in registers (mlp_chain32.hip, gemm_dw.hip), materialised for a caller that wants the tensor
+// after all.  A thread owns one 16-byte chunk of voxels of one (sample, head) — with both W-axis shifts ≡ 0 (mod 4) the four
+// voxels lie in one patch of either window — and writes it in the head's eight channel planes.
+__global__ __launch_bounds__(256) void nmf_cf_factors_to_tensor_kernel(const float* __restrict__ vf0, const float* __restrict__ uf0,
+                                                                       const float* __restrict__ vf1, const float* __restrict__ uf1,
+                                                                       float* __restrict__ out, CfGeom q, int64_t nchunk) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nchunk) return;
+  const unsigned vol = (unsigned)(q.D * q.H * q.W), per = vol >> 2;
+  const int64_t bh = i / per;
+  const unsigned vox = (unsigned)(i % per) << 2;
+  const int w = (int)(vox % (unsigned)q.W), hh = (int)((vox / (unsigned)q.W) % (unsigned)q.H), d = (int)(vox / (unsigned)(q.W * q.H));
+  const int64_t npatch = (int64_t)q.G0 * q.G1 * q.G2;
+  const float* up0 = uf0 + ((bh * npatch + cf_voxel_patch(d, hh, w, q.D, q.H, q.W, q.s0, q.s1, q.s2)) << 3);
+  const float* up1 = uf1 + ((bh * npatch + cf_voxel_patch(d, hh, w, q.D, q.H, q.W, q.ps0, q.ps1, q.ps2)) << 3);
+  const float4 v0 = ld4(vf0 + bh * vol + vox), v1 = ld4(vf1 + bh * vol + vox);
+  const float4 a0 = ld4(up0), b0 = ld4(up0 + 4), a1 = ld4(up1), b1 = ld4(up1 + 4);
+  const float u0[8] = {a0.x, a0.y, a0.z, a0.w, b0.x, b0.y, b0.z, b0.w};
+  const float u1[8] = {a1.x, a1.y, a1.z, a1.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+  for (int dd = 0; dd < 8; ++dd)
+    st4(out + (bh * 8 + dd) * vol + vox,
+        make_float4(cf_two_window_value(u0[dd], v0.x, u1[dd], v1.x), cf_two_window_value(u0[dd], v0.y, u1[dd], v1.y),
+                    cf_two_window_value(u0[dd], v0.z, u1[dd], v1.z), cf_two_window_value(u0[dd], v0.w, u1[dd], v1.w)));
+}
+
+int cf_factors_to_tensor_launch(const float* vf0, const float* uf0, const float* vf1, const float* uf1, float* out, const CfLaunch& a) {
+  const CfGeom& q = a.q;
+  const int64_t nchunk = (int64_t)q.B * q.h * ((int64_t)q.D * q.H * q.W / 4);
+  if (nchunk == 0) return FZ_OK;
+  hipLaunchKernelGGL(nmf_cf_factors_to_tensor_kernel, dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, a.st, vf0, uf0, vf1, uf1,
+                     out, q, nchunk);
+  FZ_LAUNCH_CHECK();
+  return FZ_OK;
+}
+
 }  // namespace fz

@@ -420,6 +420,58 @@ def nmf_cf_bwd_factors_supported(geo: Geometry, R, T, G, solver, relu_gate) -> b
     return ok
 
 
+_OUTPROJ_FACTORS = os.environ.get("FZ_OUTPROJ_FACTORS", "1") != "0"   # diagnostics: 0 = the core stores its output a
+
+
+def outproj_factors_supported(geo: Geometry, Hd, R, T, G, act_dtype, dropout) -> bool:
+    """where nmf_cf_factors_supported holds at C = 32, hidden 64, fp32 storage, split-bf16 products, without dropout: both
+    windows of the core leave their factors and the out-projection's two launches rebuild a from them (fz_mlp_chain_fac,
+    fz_gemm_dw_fac, include/factorizer_hip.h) — a is never stored.  FZ_OUTPROJ_FACTORS=0: the stored tensor."""
+    if not _OUTPROJ_FACTORS or len(geo.spatial) != 3:
+        return False
+    k = ("outproj", int(Hd), int(R), int(T), int(G), int(act_dtype), N.products(), bool(dropout))
+    ok = geo._factors_ok.get(k)         # asked once per configuration, not per forward
+    if ok is None:
+        ok = geo._factors_ok[k] = bool(N.lib().fz_outproj_factors_supported(
+            geo.C, k[1], *geo.spatial, geo.d, *geo.patch, *k[2:5], geo.nshift, geo._carr, k[5], k[6], int(k[7])))
+    return ok
+
+
+def core_factors(t, u0, v0, geo: Geometry, T, solver, eps):
+    """The forward core of a two-window rank-1 geometry (nmf_cf_factors_supported) as the factors of BOTH windows:
+    (vfac0, ufac0, vfac1, ufac1) — v one plane per head, u 8 floats per patch, per window; 1.13 passes over t per window and no
+    output tensor.  factors_to_tensor forms FactCoreFn's output from them, bit for bit."""
+    t, u0, v0 = t.contiguous(), u0.contiguous(), v0.contiguous()
+    B = t.shape[0]
+    nt = t.element_size() * t.numel()
+    launch, sp, shifts = _core_launches(t, geo, N.act_dtype(t))
+    nf = 4 * (t.numel() // 8)
+    fac = []
+    with _dev_guard(t):
+        for w in range(2):
+            vfac = torch.empty((B, geo.h, *geo.spatial), device=t.device, dtype=torch.float32)
+            ufac = torch.empty((B * geo.h * geo.G, 8), device=t.device, dtype=torch.float32)
+            N.set_tile_order(w)           # window 1 walks the tiles backwards (_native.py: set_tile_order)
+            launch("fz_nmf_cf_fwd_store_factors", "nmf_cf_fwd_" + sp, nt + nf, t.data_ptr(), u0.data_ptr(), v0.data_ptr(),
+                   vfac.data_ptr(), ufac.data_ptr(), B, geo.C, *geo.spatial, shifts[w], u0.shape[1], T, N.SOLVER_ID[solver], eps)
+            fac += [vfac, ufac]
+        N.set_tile_order(0)
+    return tuple(fac)
+
+
+def factors_to_tensor(fac, geo: Geometry, like):
+    """a = ((0 + u0 v0ᵀ) + u1 v1ᵀ) / 2 of core_factors' result as a tensor like `like` (fz_nmf_cf_factors_to_tensor)"""
+    out = torch.empty_like(like)
+    B = like.shape[0]
+    s0, s1 = [(N._i * 3)(*s) for s in geo.shifts3]
+    with _dev_guard(like):
+        rc = _timed("nmf_cf_factors_to_tensor", like.element_size() * like.numel() * 5 // 4,
+                    lambda: N.lib().fz_nmf_cf_factors_to_tensor(*(f.data_ptr() for f in fac), out.data_ptr(), B, geo.C, *geo.spatial,
+                                                                s0, s1, N.act_dtype(like), N.stream_ptr(like)))
+    N.check(rc, "fz_nmf_cf_factors_to_tensor")
+    return out
+
+
 def nmf_pcf_supported(geo: Geometry, R, T, G) -> bool:
     """the generic-patch fused core (csrc/nmf_pcf.hip): head_dim 8, <= 256 voxels per patch, any shift.  1-D and 2-D tensors
     (operations.py:318-325 is N-D generic; the reference's own test models are 2-D) run as depth-1 (and height-1) volumes:

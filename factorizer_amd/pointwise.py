@@ -197,10 +197,14 @@ def _dw_fused_ok(C, V):
     return C == 32 and V % 4 == 0 and V <= (1 << 27) and os.environ.get("FZ_DW_FUSED", "1") != "0"
 
 
-def _gemm_dw(g, w2, q, ln=None, stats=None, gadd=None, want_bias=False, name="dgrad_wgrad", gw_out=None, gb_out=None, drop=None):
+def _gemm_dw(g, w2, q, ln=None, stats=None, gadd=None, want_bias=False, name="dgrad_wgrad", gw_out=None, gb_out=None, drop=None,
+             fac=None):
     """y = Wᵀ g [→ LayerNorm backward + gadd], gw = Σ_v g ⊗ in, gb = Σ_v g — fz_gemm_dw.  ln = (γ, β) or None.
     drop = (keep bits, p): g is read as keep·g/(1 − p) (block dropout site 0, no ln).
+    fac = (core factors, geometry) with q None: the layer input is the core's output, rebuilt from the factors in the kernel.
     Returns (y, gw, gb or None, gγ, gβ) (gγ, gβ None without ln)."""
+    if fac is not None:
+        q = g                     # (shape, type and device of the operand that is not stored)
     B, C = q.shape[:2]
     V = _vox(q)
     dev = q.device
@@ -210,7 +214,8 @@ def _gemm_dw(g, w2, q, ln=None, stats=None, gadd=None, want_bias=False, name="dg
     gb = (gb_out if gb_out is not None else torch.empty(C, dtype=torch.float32, device=dev)) if want_bias else None
     wpart = torch.empty(N.lib().fz_gemm_dw_workspace_bytes(B, V) // 4, dtype=torch.float32, device=dev)
     d = N.GemmDwDesc()
-    d.g, d.q, d.w, d.y = g.data_ptr(), q.data_ptr(), w2.data_ptr(), y.data_ptr()
+    d.g, d.q, d.w, d.y = g.data_ptr(), q.data_ptr() if fac is None else None, w2.data_ptr(), y.data_ptr()
+    df = N.outproj_fac(*fac) if fac is not None else None
     d.wpart, d.gw, d.gb = wpart.data_ptr(), gw.data_ptr(), _p(gb)
     d.B, d.C, d.V, d.act_dtype = B, C, V, N.act_dtype(q)
     d.ldgw = gw.stride(0)
@@ -221,9 +226,12 @@ def _gemm_dw(g, w2, q, ln=None, stats=None, gadd=None, want_bias=False, name="dg
     if ln is not None:
         gpar = torch.empty(64, dtype=torch.float32, device=dev)
         d.ln, d.stats, d.ln_g, d.ln_b, d.gadd, d.gln = 1, stats.data_ptr(), ln[0].data_ptr(), ln[1].data_ptr(), _p(gadd), gpar.data_ptr()
-    nbytes = q.element_size() * (3 * q.numel() + (gadd.numel() if gadd is not None else 0))
+    # (the factor form reads two v fields of q.numel() / 8 floats in place of q)
+    nbytes = q.element_size() * ((3 * q.numel() if fac is None else 2 * q.numel() + q.numel() // 4) + (gadd.numel() if gadd is not None else 0))
     with torch.cuda.device(dev), _finish_scope(wpart, gw, gb, gpar):
-        rc = Fn._timed(f"{name}_{C}", nbytes, lambda: N.lib().fz_gemm_dw(ctypes.byref(d), N.stream_ptr(q)),
+        rc = Fn._timed(f"{name}_{C}", nbytes,
+                       lambda: (N.lib().fz_gemm_dw(ctypes.byref(d), N.stream_ptr(q)) if df is None
+                                else N.lib().fz_gemm_dw_fac(ctypes.byref(d), ctypes.byref(df), N.stream_ptr(q))),
                        cols=B * V, flops=4 * B * V * C * C)
         N.check(rc, "fz_gemm_dw")
     if ln is not None:
@@ -271,10 +279,11 @@ def _mlp_desc(mode, like, w12, w22, *, B, C, Hd, V, inp=None, b1=None, b2=None, 
     return d
 
 
-def _mlp_chain_fwd(timed, like, ln_w, ln_b, eps, w12, b1, w22, b2, inp=None, pre=None, head=None, drop=None):
+def _mlp_chain_fwd(timed, like, ln_w, ln_b, eps, w12, b1, w22, b2, inp=None, pre=None, head=None, drop=None, fac=None):
     """The forward chain launch (fz_mlp_chain mode 0) under `timed` = (timer key, algorithmic bytes, flops): x2 = x1 + fc2(gelu(
     fc1(LN(x1)))) with x1 = `inp`, or — pre = (a, wout2, bout, x) — x1 = x + out_proj(a) formed on the accumulators in front of
-    the chain and written once.  head = (weight (M, C), bias or None): the logits of x2 in the same launch; drop: `_mlp_dropout`.
+    the chain and written once (fac = (core factors, geometry) with a None: a is rebuilt from the factors in the kernel).
+    head = (weight (M, C), bias or None): the logits of x2 in the same launch; drop: `_mlp_dropout`.
     Returns (x1 or None, x2, z1, statistics, logits or None)."""
     B, C = like.shape[:2]
     V = _vox(like)
@@ -286,18 +295,26 @@ def _mlp_chain_fwd(timed, like, ln_w, ln_b, eps, w12, b1, w22, b2, inp=None, pre
     if pre is not None:
         a, wout2, bout, x = pre
         x1 = torch.empty_like(like)
-        d.pre_in, d.pre_w, d.pre_b, d.pre_res, d.pre_out = a.data_ptr(), wout2.data_ptr(), _p(bout), x.data_ptr(), x1.data_ptr()
+        d.pre_in, d.pre_w, d.pre_b, d.pre_res, d.pre_out = _p(a), wout2.data_ptr(), _p(bout), x.data_ptr(), x1.data_ptr()
     if head is not None:
         hw, hb = head
         logits = new(hw.shape[0])
         d.post_w, d.post_b, d.post_out, d.post_m = hw.data_ptr(), _p(hb), logits.data_ptr(), hw.shape[0]
     dd = _mlp_dropout(drop) if drop is not None else None   # block dropout: the three sites inside this launch
+    df = N.outproj_fac(*fac) if fac is not None else None   # the core's factors in place of a (never with dropout: the library refuses)
+    if dd is not None and df is not None:
+        raise N.NativeError("fz_mlp_chain: no dropout form of the chain on the core's factors")
     key, nbytes, flops = timed
+
+    def run():
+        if df is not None:
+            return N.lib().fz_mlp_chain_fac(ctypes.byref(d), ctypes.byref(df), N.stream_ptr(like))
+        if dd is not None:
+            return N.lib().fz_mlp_chain_drop(ctypes.byref(d), ctypes.byref(dd), N.stream_ptr(like))
+        return N.lib().fz_mlp_chain(ctypes.byref(d), N.stream_ptr(like))
+
     with torch.cuda.device(like.device):
-        rc = Fn._timed(key, nbytes,
-                       lambda: (N.lib().fz_mlp_chain(ctypes.byref(d), N.stream_ptr(like)) if dd is None
-                                else N.lib().fz_mlp_chain_drop(ctypes.byref(d), ctypes.byref(dd), N.stream_ptr(like))),
-                       cols=B * V, flops=flops)
+        rc = Fn._timed(key, nbytes, run, cols=B * V, flops=flops)
     N.check(rc, "fz_mlp_chain")
     return x1, x2, z1, st, logits
 
@@ -321,17 +338,28 @@ def _outproj_mlp_ok(C, Hd, V):
     return _OUTPROJ_MLP and _mlp_chain_ok(C, Hd, V) and bool(N.lib().fz_mlp_pre_supported(C, Hd, V, N.products()))
 
 
-def _outproj_mlp_fwd_chain(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2, head=None, drop=None):
+def _outproj_factors_ok(x, geo, Hd, R, T, G, drop):
+    """the block's out-projection takes the core's output as the rank-1 factors of its two windows, forward (inside the chain
+    launch) and backward (inside fz_gemm_dw): fz_outproj_factors_supported, where both of those launches are what the block runs"""
+    C, V = x.shape[1], _vox(x)
+    return (drop is None and isinstance(geo, Fn.Geometry) and _outproj_mlp_ok(C, Hd, V) and _dw_fused_ok(C, V)
+            and Fn.outproj_factors_supported(geo, Hd, R, T, G, N.act_dtype(x), False))
+
+
+def _outproj_mlp_fwd_chain(a, wout2, bout, x, ln_w, ln_b, eps, w12, b1, w22, b2, head=None, drop=None, fac=None):
     """x1 = x + out_proj(a) (factorizer.py:53,75) and x2 = x1 + fc2(gelu(fc1(LN(x1)))) (factorizer.py:76; mlp.py:54-63) in ONE
     launch: the out-projection runs on the accumulators in front of the chained MLP GEMMs, x1 is written once (the backward
     needs it) and never read back — 6 instead of 7 tensor passes.  Returns (x1, x2, z1, stats), plus the logits when `head` =
-    (weight (M, C), bias or None) of the network's head Linear(C -> M <= 4) is given: it is applied to x2 in the same launch."""
-    B, C = a.shape[:2]
-    V = _vox(a)
+    (weight (M, C), bias or None) of the network's head Linear(C -> M <= 4) is given: it is applied to x2 in the same launch.
+    fac = (core factors, geometry) with a None: the launch reads two v fields of an eighth of a tensor each in place of a."""
+    B, C = x.shape[:2]
+    V = _vox(x)
     Hd = w12.shape[0]
     nlogits = B * head[0].shape[0] * V if head is not None else 0
-    timed = (f"outproj_mlp_chain_fwd_{C}", a.element_size() * (4 * a.numel() + B * Hd * V + nlogits), 4 * B * V * C * Hd + 2 * B * V * C * C)
-    x1, x2, z1, st, logits = _mlp_chain_fwd(timed, a, ln_w, ln_b, eps, w12, b1, w22, b2, pre=(a, wout2, bout, x), head=head, drop=drop)
+    na = x.numel() if fac is None else x.numel() // 4
+    timed = (f"outproj_mlp_chain_fwd_{C}", x.element_size() * (3 * x.numel() + na + B * Hd * V + nlogits), 4 * B * V * C * Hd + 2 * B * V * C * C)
+    x1, x2, z1, st, logits = _mlp_chain_fwd(timed, x, ln_w, ln_b, eps, w12, b1, w22, b2, pre=(a, wout2, bout, x), head=head, drop=drop,
+                                            fac=fac)
     if head is not None:
         return x1, x2, z1, st, logits
     return x1, x2, z1, st
@@ -1517,8 +1545,13 @@ class FactorizerBlockFn(torch.autograd.Function):
             _gemm([x], win2, t, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, ln=(n1w, n1b, cfg["eps1"]), stats_out=st1,
                   eact=ACT["relu"], name="ln_linear")
         # 2. a = inverse(NMF(matricize(t)))
-        m = None
-        if cfg["core"]:
+        m = fac = None
+        R = u0c.shape[1]
+        if cfg["core"] and _outproj_factors_ok(x, geo, Hd, R, T, G, drop):
+            # both windows leave their rank-1 factors and the out-projection's launches, forward and backward, rebuild a from
+            # them: a is never stored (2.5 passes over a tensor less per block, one tensor less saved)
+            a, fac = None, (Fn.core_factors(t, u0c, v0c, geo, T, solver, neps), geo)
+        elif cfg["core"]:
             a = Fn.FactCoreFn.forward(_Ctx(), t, u0c, v0c, geo, T, G, solver, neps, True)
         else:
             m = Fn._swm_fwd_raw(t, geo)
@@ -1528,10 +1561,11 @@ class FactorizerBlockFn(torch.autograd.Function):
         # 3. x1 = x + out_proj(a)   4. z1 = fc1(LN2(x1)) ; x2 = x1 + fc2(gelu(z1))
         logits = None
         tail = (a, wout2, bout, x, n2w, n2b, cfg["eps2"], w12, b1, w22, b2)
-        if (_mlp_drop_ok if drop is not None else _outproj_mlp_ok)(C, Hd, V) and a.is_contiguous():
+        if (_mlp_drop_ok if drop is not None else _outproj_mlp_ok)(C, Hd, V) and (fac is not None or a.is_contiguous()):
             # both in one launch; the README block's three masks are read inside it, else the head, when asked, is applied to x2 in it
             head = (head_w.reshape(head_w.shape[0], C), head_b) if head_w is not None and drop is None else None
-            x1, x2, z1, st2, *logits = _outproj_mlp_fwd_chain(*tail, head=head, drop=(bits, drop) if drop is not None else None)
+            x1, x2, z1, st2, *logits = _outproj_mlp_fwd_chain(*tail, head=head, drop=(bits, drop) if drop is not None else None,
+                                                              **({"fac": fac} if fac is not None else {}))
             logits = logits[0] if logits else None
         elif drop is None and _mlp_chain_ok(C, Hd, V):
             x1 = new(C)
@@ -1539,7 +1573,8 @@ class FactorizerBlockFn(torch.autograd.Function):
             x2, z1, st2 = _mlp_fwd_chain(x1, n2w, n2b, cfg["eps2"], w12, b1, w22, b2)
         else:
             x1, x2, z1, st2 = _block_tail_fwd(*tail, drop, bits)
-        ctx.save_for_backward(x, st1, t, a, x1, st2, z1, m, n1w, n1b, win2, u0c, v0c, wout2, n2w, n2b, w12, w22, *bits)
+        ctx.save_for_backward(x, st1, t, a, x1, st2, z1, m, n1w, n1b, win2, u0c, v0c, wout2, n2w, n2b, w12, w22, *bits,
+                              *(fac[0] if fac is not None else ()))
         ctx.cfg = cfg
         ctx.shapes = (win.shape, wout.shape, w1.shape, w2.shape)
         ctx.prm = tuple(weakref.ref(t) for t in (win, wout, bout, w1, b1, w2, b2))
@@ -1556,6 +1591,7 @@ class FactorizerBlockFn(torch.autograd.Function):
     @_bwd
     def backward(ctx, g2, _g_logits=None):
         x, st1, t, a, x1, st2, z1, m, n1w, n1b, win2, u0c, v0c, wout2, n2w, n2b, w12, w22, *bits = ctx.saved_tensors
+        bits, fac = bits[:3], (tuple(bits[3:]), ctx.cfg["geo"]) if len(bits) > 3 else None   # (the core's factors in place of a)
         cfg = ctx.cfg
         drop = cfg.get("drop")
         if g2 is None:
@@ -1628,8 +1664,11 @@ class FactorizerBlockFn(torch.autograd.Function):
         # --- out_proj ---
         dw = _dw_fused_ok(C, V)
         if dw:
-            ga, gwo, gbo, _, _ = _gemm_dw(go, wout2, a, want_bias=True, name="dgrad_wgrad", drop=go_drop)
+            ga, gwo, gbo, _, _ = _gemm_dw(go, wout2, a, want_bias=True, name="dgrad_wgrad", drop=go_drop,
+                                          **({"fac": fac} if fac is not None else {}))
         else:
+            if fac is not None:   # (FZ_DW_FUSED switched off between forward and backward: the tensor after all)
+                a = Fn.factors_to_tensor(*fac, x)
             ga = torch.empty_like(a)
             _gemm([go], wout2, ga, B=B, Cin=C, Vin=V, M=C, K=C, Ncol=V, w_t=True, ldw=C, name="linear_dgrad")
             gwo = _GB.out_like(wout2)

@@ -221,6 +221,17 @@ int fz_nmf_cf_bwd(const void* t, const float* u0, const float* v0, const void* g
  * fz_nmf_cf_fwd once per window.  The backward recomputes from t either way (fz_nmf_cf_bwd, or the pair below). */
 int fz_nmf_cf_factors_supported(int C, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
                                 int nshift, const int* shifts);
+/* a = ((0 + u0 v0^T) + u1 v1^T) / 2 in one pass from the factors that fz_nmf_cf_fwd_store_factors left for window 0
+ * (shift0) and for window 1 (shift1): bit for bit the `out` of fz_nmf_cf_fwd_store_factors + fz_nmf_cf_fwd_from_factors with
+ * divisor 2.  fp32 storage only (FZ_E_UNSUPPORTED for bf16); same shape conditions as the pair. */
+int fz_nmf_cf_factors_to_tensor(const float* vfac0, const float* ufac0, const float* vfac1, const float* ufac1, void* out,
+                                int B, int C, int D, int H, int W, const int* shift0, const int* shift1, int act_dtype,
+                                fz_stream_t stream);
+/* 1 where the out-projection's two launches at C = 32 take a as those factors and a is never stored (fz_mlp_chain_fac,
+ * fz_gemm_dw_fac): fz_nmf_cf_factors_supported holds, C == 32, hidden Hd == 64, fp32 storage, split-bf16 products
+ * (fz_mlp_pre_supported), no live dropout, exactly two windows. */
+int fz_outproj_factors_supported(int C, int Hd, int D, int H, int W, int d, int pd, int ph, int pw, int R, int T, int Tgrad,
+                                 int nshift, const int* shifts, int act_dtype, int products, int dropout);
 int fz_nmf_cf_fwd_store_factors(const void* t, const float* u0, const float* v0, float* vfac, float* ufac, int B,
                                 int C, int D, int H, int W, const int* shift, int R, int T, int solver, float eps,
                                 int act_dtype, fz_stream_t stream);
@@ -488,6 +499,27 @@ typedef struct fz_gemm_dw_desc {
 int fz_gemm_dw_rows(int B, int64_t V);
 int64_t fz_gemm_dw_workspace_bytes(int B, int64_t V);
 int fz_gemm_dw(const fz_gemm_dw_desc* desc, fz_stream_t stream);
+
+/* ---- the out-projection on the core's rank-1 factors (C = 32, where fz_outproj_factors_supported) ----
+ * The core's output a is not a tensor but the factors that BOTH windows of the core left (fz_nmf_cf_fwd_store_factors called
+ * once per window); the two launches that read a rebuild their operand tiles of it in registers, with the bits of
+ * fz_nmf_cf_factors_to_tensor, so every value behind them is the one the stored tensor gives.
+ *   fz_mlp_chain_fac: fz_mlp_chain mode 0 with the out-projection in front (pre_w, pre_b, pre_res, pre_out, post_* as with
+ *     pre_in; pre_in itself NULL).  Refused with FZ_E_UNSUPPORTED outside (C, H) = (32, 64), mode 0, fp32 storage,
+ *     split-bf16 products (fz_mlp_pre_supported); there is no dropout form.
+ *   fz_gemm_dw_fac: fz_gemm_dw with q NULL (the layer input is a).  Refused with FZ_E_UNSUPPORTED with ln, drop_m or bf16
+ *     storage.
+ * Both check the factors against the launch: heads == 4, dims multiples of 8 with W % 64 == 0 and D H W == V, W-axis shifts
+ * multiples of 4.  Descriptor layouts and the entry points that take a stored tensor are unchanged (no ABI revision). */
+typedef struct fz_outproj_fac {
+  const float* v[2];  /* per window: (B, heads, D, H, W) v at the true voxel positions   */
+  const float* u[2];  /* per window: (B * heads * D/8 * H/8 * W/8, 8) u per patch         */
+  int dims[3];        /* D, H, W                                                          */
+  int heads;          /* C / 8 = 4                                                        */
+  int shift[6];       /* the two windows' shifts, three ints each                         */
+} fz_outproj_fac;
+int fz_mlp_chain_fac(const fz_mlp_desc* desc, const fz_outproj_fac* fac, fz_stream_t stream);
+int fz_gemm_dw_fac(const fz_gemm_dw_desc* desc, const fz_outproj_fac* fac, fz_stream_t stream);
 
 /* ---- backward of a Linear(32 -> M), M <= 4, in one pass (the network's head: factorizer/unet.py:253) ----
  * gx = W^T gy (activation, (B, 32, V)); weight and bias gradient as fz_head_bwd_rows() partial rows of 132 floats

@@ -261,6 +261,13 @@ _SIGS.update({
     "fz_gnmfx_launches": ([_i, _i64, _i, _i, _i, _i], _i),
     "fz_gnmfx_fwd": ([_vp] * 6 + [_i64, _i, _i64, _i, _i, _i, _f, _vp, _vp], _i),
     "fz_gnmfx_bwd": ([_vp] * 7 + [_i64, _i, _i64, _i, _i, _i, _i, _f, _vp, _vp], _i),
+    # the two split-N families on either activation storage type (act_dtype before the workspace)
+    "fz_gnmf_workspace_bytes_act": ([_i64, _i, _i64, _i, _i, _i, _i], _i64),
+    "fz_gnmf_fwd_act": ([_vp] * 6 + [_i64, _i, _i64, _i, _i, _i, _f, _i, _vp, _vp], _i),
+    "fz_gnmf_bwd_act": ([_vp] * 7 + [_i64, _i, _i64, _i, _i, _i, _i, _f, _i, _vp, _vp], _i),
+    "fz_gnmfx_workspace_bytes_act": ([_i64, _i, _i64, _i, _i, _i, _i], _i64),
+    "fz_gnmfx_fwd_act": ([_vp] * 6 + [_i64, _i, _i64, _i, _i, _i, _f, _i, _vp, _vp], _i),
+    "fz_gnmfx_bwd_act": ([_vp] * 7 + [_i64, _i, _i64, _i, _i, _i, _i, _f, _i, _vp, _vp], _i),
     "fz_nmf_cf_supported": ([_i] * 11, _i),
     "fz_nmf_cf_fwd": ([_vp] * 4 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 5 + [_f, _i, _vp], _i),
     "fz_nmf_cf_bwd": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 7 + [_f, _i, _vp], _i),

@@ -280,7 +280,7 @@ def nmf_decompose(x, u0, v0, T, G, solver, eps=1e-16):
 
 # ---- split-N NMF: matrices too wide for one wavefront ----------------------------
 # two kernel families with one argument list: "gnmf" (csrc/nmf_global.hip: M <= 64, rank <= 4) and "gnmfx"
-# (csrc/nmf_global_rank.hip: 16 <= M <= 512, rank <= 32, MU / HALS)
+# (csrc/nmf_global_rank.hip: 16 <= M <= 512, rank <= 32, MU / HALS); fp32 or bf16 activation storage
 def gnmf_supported(M, N_, R, T, G) -> bool:
     return bool(N.lib().fz_gnmf_supported(int(M), int(N_), int(R), int(T), int(G)))
 
@@ -290,28 +290,30 @@ def gnmfx_supported(M, N_, R, T, G) -> bool:
 
 
 def _gnmf_ws(x, nmat, M, Nn, R, T, backward, fam="gnmf"):
-    nb = getattr(N.lib(), f"fz_{fam}_workspace_bytes")(nmat, M, Nn, R, T, int(backward))
+    nb = getattr(N.lib(), f"fz_{fam}_workspace_bytes_act")(nmat, M, Nn, R, T, int(backward), N.act_dtype(x))
     if nb < 0:
-        raise N.NativeError(f"fz_{fam}_workspace_bytes failed")
+        raise N.NativeError(f"fz_{fam}_workspace_bytes_act failed")
     return torch.empty(max(nb // 4, 1), dtype=torch.float32, device=x.device)
 
 
 def _gnmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=False, fam="gnmf"):
+    """x fp32 or bf16 storage; y has the dtype of x, the factors are always fp32 (as _nmf_fwd_raw returns them)"""
     M, Nn = x.shape[-2:]
     R = u0.shape[1]
     nmat = x.numel() // (M * Nn)
     y = torch.empty_like(x)
     u = v = None
     if want_uv:
-        u = torch.empty((*x.shape[:-2], M, R), dtype=x.dtype, device=x.device)
-        v = torch.empty((*x.shape[:-2], Nn, R), dtype=x.dtype, device=x.device)
+        u = torch.empty((*x.shape[:-2], M, R), dtype=torch.float32, device=x.device)
+        v = torch.empty((*x.shape[:-2], Nn, R), dtype=torch.float32, device=x.device)
     ws = _gnmf_ws(x, nmat, M, Nn, R, T, False, fam)
-    fwd = getattr(N.lib(), f"fz_{fam}_fwd")
+    fwd = getattr(N.lib(), f"fz_{fam}_fwd_act")
+    ad = N.act_dtype(x)
     with _dev_guard(x):
-        rc = _timed(f"{fam}_fwd_{M}x{Nn}", 2 * x.numel() * 4, lambda: fwd(
+        rc = _timed(f"{fam}_fwd_{M}x{Nn}", 2 * x.numel() * x.element_size(), lambda: fwd(
             x.data_ptr(), u0.data_ptr(), v0.data_ptr(), y.data_ptr(), N.ptr(u), N.ptr(v), nmat, M, Nn, R, T,
-            N.SOLVER_ID[solver], eps, ws.data_ptr(), N.stream_ptr(x)))
-    N.check(rc, f"fz_{fam}_fwd")
+            N.SOLVER_ID[solver], eps, ad, ws.data_ptr(), N.stream_ptr(x)))
+    N.check(rc, f"fz_{fam}_fwd_act")
     return y, u, v
 
 
@@ -320,13 +322,18 @@ def _gnmf_bwd_raw(x, u0, v0, gy, gu, gv, T, G, solver, eps, fam="gnmf"):
     R = u0.shape[1]
     nmat = x.numel() // (M * Nn)
     gx = torch.empty_like(x)
+    if gy is not None and gy.dtype != x.dtype:
+        gy = gy.to(x.dtype)
+    if gu is not None:
+        gu, gv = gu.float().contiguous(), gv.float().contiguous()
     ws = _gnmf_ws(x, nmat, M, Nn, R, T, True, fam)
-    bwd = getattr(N.lib(), f"fz_{fam}_bwd")
+    bwd = getattr(N.lib(), f"fz_{fam}_bwd_act")
+    ad = N.act_dtype(x)
     with _dev_guard(x):
-        rc = _timed(f"{fam}_bwd_{M}x{Nn}", 3 * x.numel() * 4, lambda: bwd(
+        rc = _timed(f"{fam}_bwd_{M}x{Nn}", 3 * x.numel() * x.element_size(), lambda: bwd(
             x.data_ptr(), u0.data_ptr(), v0.data_ptr(), N.ptr(gy), N.ptr(gu), N.ptr(gv), gx.data_ptr(), nmat, M, Nn,
-            R, T, G, N.SOLVER_ID[solver], eps, ws.data_ptr(), N.stream_ptr(x)))
-    N.check(rc, f"fz_{fam}_bwd")
+            R, T, G, N.SOLVER_ID[solver], eps, ad, ws.data_ptr(), N.stream_ptr(x)))
+    N.check(rc, f"fz_{fam}_bwd_act")
     return gx
 
 

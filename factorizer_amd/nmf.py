@@ -432,7 +432,8 @@ class MatrixFactorization(nn.Module):
         G = min(max(self.num_grad_steps, 0), self.num_iters)
         if not Fn.nmf_supported(self.size[0], self.size[1], self.rank, self.num_iters, G):
             # wider than one wavefront can hold (global Matricize, num_heads= forms): the split-N kernels
-            if x.dtype == torch.float32 and x.numel() // (self.size[0] * self.size[1]) <= 65535:
+            # (fp32 or bf16 storage, as the wave-resident kernels)
+            if x.numel() // (self.size[0] * self.size[1]) <= 65535:
                 if Fn.gnmf_supported(self.size[0], self.size[1], self.rank, self.num_iters, G):
                     self._wide = "gnmf"
                     return sid

@@ -55,7 +55,7 @@ int fz_version(void);
  * compares fz_abi_version() with the FZ_ABI_VERSION of the header it was written against BEFORE the first call and refuses
  * to run on a mismatch (factorizer_amd/_native.py does).  History: 3 = round 3; 4 = round 4 (`products` / `tune` descriptor
  * fields, `products` argument of fz_conv3_*); 5 = round 5 (the two-window entry points fz_nmf_cf_fwd2 / _bwd2 removed, this
- * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words; fz_gcorr_act / fz_gcorr_wgrad_act / fz_gcorr_mu_bwd: the grouped correlations on bf16 storage; fz_dice_bce_ds_* / fz_dice_ce_ds_*: the deep-supervision levels of the loss; fz_gemm_plan: the dry run of fz_gemm's dispatcher) leave it at 7. */
+ * function added); 6 = round 6 (fz_finish_defer is per THREAD, one finish queue per stream, fz_finish_flush_all added, fz_gemm_dw_desc.ldw); 7 = block dropout (fz_dropout_* and fz_mlp_drop_supported, fz_mlp_chain_drop added, fz_gemm_dw_desc.drop_m / drop_s appended); entry points added since without touching an existing signature or descriptor (fz_vol_*, fz_vol_respace / fz_vol_unspace, fz_aug_crop_resample / fz_aug_source_words; fz_gcorr_act / fz_gcorr_wgrad_act / fz_gcorr_mu_bwd: the grouped correlations on bf16 storage; fz_dice_bce_ds_* / fz_dice_ce_ds_*: the deep-supervision levels of the loss; fz_gemm_plan: the dry run of fz_gemm's dispatcher; fz_gnmf_fwd_act / _bwd_act / _workspace_bytes_act and fz_gnmfx_fwd_act / _bwd_act / _workspace_bytes_act: the split-N NMF families on bf16 storage) leave it at 7. */
 #define FZ_ABI_VERSION 7
 int fz_abi_version(void);
 /* Walking order of the fused-core launches (fz_nmf_cf_fwd / fz_nmf_cf_bwd) this THREAD issues from now on: 0 = ascending over
@@ -161,6 +161,22 @@ int fz_gnmf_fwd(const float* x, const float* u0, const float* v0, float* y, floa
 int fz_gnmf_bwd(const float* x, const float* u0, const float* v0, const float* gy, const float* gu,
                 const float* gv, float* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad, int solver,
                 float eps, void* workspace, fz_stream_t stream);
+/* The same on either activation storage type: x, gy, y, gx are (nmat, M, N) fp32 (FZ_STORE_F32) or bf16 (FZ_STORE_BF16)
+ * matrices; any other act_dtype is refused (FZ_E_ARG).  Only storage differs: x and gy become fp32 as they are loaded, each
+ * y and gx element is rounded to nearest-even once as it is stored, and u0, v0, u_out, v_out, gu, gv, the factors, Gram
+ * matrices and the order of every sum are those of the fp32 call — y and gx are the fp32 call's results on the same values,
+ * rounded.  A bf16 matrix needs 2-byte alignment only (wider accesses are used where base and N allow them).
+ * fz_gnmf_fwd / fz_gnmf_bwd are these with FZ_STORE_F32; supported shapes, refusals and launch counts do not depend on
+ * act_dtype.  workspace: fz_gnmf_workspace_bytes_act(..., act_dtype) bytes; with FZ_STORE_F32 that is
+ * fz_gnmf_workspace_bytes(...), and so it is for a bf16 forward; a bf16 BACKWARD adds nmat*M*N floats, the fp32 running
+ * sum of gx over the launches that add to it (-1: unsupported shape, nmat < 0 or an act_dtype outside FZ_STORE_*). */
+int64_t fz_gnmf_workspace_bytes_act(int64_t nmat, int M, int64_t N, int R, int T, int backward, int act_dtype);
+int fz_gnmf_fwd_act(const void* x, const float* u0, const float* v0, void* y, float* u_out, float* v_out,
+                    int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, int act_dtype,
+                    void* workspace, fz_stream_t stream);
+int fz_gnmf_bwd_act(const void* x, const float* u0, const float* v0, const void* gy, const float* gu, const float* gv,
+                    void* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad, int solver, float eps,
+                    int act_dtype, void* workspace, fz_stream_t stream);
 
 /* ---- split-N NMF for ranks up to 32 and matrices up to 512 rows (csrc/nmf_global_rank.hip) -------------
  * The reference's default-constructed model: Matricize(num_heads=1, grid_size=1) with rank=None, i.e.
@@ -180,6 +196,16 @@ int fz_gnmfx_fwd(const float* x, const float* u0, const float* v0, float* y, flo
 int fz_gnmfx_bwd(const float* x, const float* u0, const float* v0, const float* gy, const float* gu,
                  const float* gv, float* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad, int solver,
                  float eps, void* workspace, fz_stream_t stream);
+/* The same on either activation storage type, exactly as fz_gnmf_fwd_act / fz_gnmf_bwd_act / fz_gnmf_workspace_bytes_act
+ * relate to fz_gnmf_*: fz_gnmfx_fwd / fz_gnmfx_bwd are these with FZ_STORE_F32, and a bf16 backward's workspace holds
+ * nmat*M*N more floats. */
+int64_t fz_gnmfx_workspace_bytes_act(int64_t nmat, int M, int64_t N, int R, int T, int backward, int act_dtype);
+int fz_gnmfx_fwd_act(const void* x, const float* u0, const float* v0, void* y, float* u_out, float* v_out,
+                     int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, int act_dtype,
+                     void* workspace, fz_stream_t stream);
+int fz_gnmfx_bwd_act(const void* x, const float* u0, const float* v0, const void* gy, const float* gu, const float* gv,
+                     void* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad, int solver, float eps,
+                     int act_dtype, void* workspace, fz_stream_t stream);
 
 /* ---- FactMixer core on channels-first tensors (hot shape: head_dim 8, patch 8x8x8) -----------
  * One launch per shift window performs SWMatricize.forward → NMF.forward →

@@ -243,6 +243,20 @@ class RespaceGeom(_c.Structure):
                 ("inv_scale", _c.c_double * 3)]
 
 
+def _wide_nmf_sigs(fam):
+    """the entry points that the two split-N NMF families have alike (csrc/nmf_wide.h): the fp32 ones, and the `_act` ones with
+    act_dtype before the workspace"""
+    shape = [_i64, _i, _i64, _i, _i]                 # nmat M N R T
+    fwd = [_vp] * 6 + shape + [_i, _f]               # x u0 v0 y u_out v_out | shape | solver eps
+    bwd = [_vp] * 7 + shape + [_i, _i, _f]           # x u0 v0 gy gu gv gx | shape | Tgrad solver eps
+    out = {f"fz_{fam}_supported": ([_i, _i64, _i, _i, _i], _i)}
+    for sfx, act in (("", []), ("_act", [_i])):
+        out[f"fz_{fam}_workspace_bytes{sfx}"] = (shape + [_i] + act, _i64)          # ... backward [act_dtype]
+        out[f"fz_{fam}_fwd{sfx}"] = (fwd + act + [_vp, _vp], _i)                    # ... [act_dtype] workspace stream
+        out[f"fz_{fam}_bwd{sfx}"] = (bwd + act + [_vp, _vp], _i)
+    return out
+
+
 _SIGS.update({
     "fz_gcorr_supported": ([_i] * 5, _i),
     "fz_gcorr": ([_vp] * 5 + [_i] * 11 + [_f, _vp], _i),
@@ -251,23 +265,10 @@ _SIGS.update({
     "fz_gcorr_act": ([_vp] * 5 + [_i] * 11 + [_f, _i, _vp], _i),
     "fz_gcorr_wgrad_act": ([_vp] * 4 + [_i] * 12 + [_vp], _i),
     "fz_gcorr_mu_bwd": ([_vp] * 8 + [_i] * 11 + [_f, _i, _vp], _i),
-    "fz_gnmf_supported": ([_i, _i64, _i, _i, _i], _i),
-    "fz_gnmf_workspace_bytes": ([_i64, _i, _i64, _i, _i, _i], _i64),
     "fz_gnmf_launches": ([_i, _i, _i], _i),
-    "fz_gnmf_fwd": ([_vp] * 6 + [_i64, _i, _i64, _i, _i, _i, _f, _vp, _vp], _i),
-    "fz_gnmf_bwd": ([_vp] * 7 + [_i64, _i, _i64, _i, _i, _i, _i, _f, _vp, _vp], _i),
-    "fz_gnmfx_supported": ([_i, _i64, _i, _i, _i], _i),
-    "fz_gnmfx_workspace_bytes": ([_i64, _i, _i64, _i, _i, _i], _i64),
     "fz_gnmfx_launches": ([_i, _i64, _i, _i, _i, _i], _i),
-    "fz_gnmfx_fwd": ([_vp] * 6 + [_i64, _i, _i64, _i, _i, _i, _f, _vp, _vp], _i),
-    "fz_gnmfx_bwd": ([_vp] * 7 + [_i64, _i, _i64, _i, _i, _i, _i, _f, _vp, _vp], _i),
-    # the two split-N families on either activation storage type (act_dtype before the workspace)
-    "fz_gnmf_workspace_bytes_act": ([_i64, _i, _i64, _i, _i, _i, _i], _i64),
-    "fz_gnmf_fwd_act": ([_vp] * 6 + [_i64, _i, _i64, _i, _i, _i, _f, _i, _vp, _vp], _i),
-    "fz_gnmf_bwd_act": ([_vp] * 7 + [_i64, _i, _i64, _i, _i, _i, _i, _f, _i, _vp, _vp], _i),
-    "fz_gnmfx_workspace_bytes_act": ([_i64, _i, _i64, _i, _i, _i, _i], _i64),
-    "fz_gnmfx_fwd_act": ([_vp] * 6 + [_i64, _i, _i64, _i, _i, _i, _f, _i, _vp, _vp], _i),
-    "fz_gnmfx_bwd_act": ([_vp] * 7 + [_i64, _i, _i64, _i, _i, _i, _i, _f, _i, _vp, _vp], _i),
+    **_wide_nmf_sigs("gnmf"),
+    **_wide_nmf_sigs("gnmfx"),
     "fz_nmf_cf_supported": ([_i] * 11, _i),
     "fz_nmf_cf_fwd": ([_vp] * 4 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 5 + [_f, _i, _vp], _i),
     "fz_nmf_cf_bwd": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 7 + [_f, _i, _vp], _i),

@@ -111,7 +111,7 @@ class FactorizerBlock(nn.Module):
             return False
         t_like = x.new_empty((1, *f.reshape.output_size[1:]))
         # (wave-resident NMF family only: the block's hand-chained backward calls those kernels directly)
-        return mf._native_solver(t_like) is not None and not mf._wide and len(f.reshape.geometry.spatial) <= 3
+        return mf._native_solver(t_like)[1] == "nmf" and len(f.reshape.geometry.spatial) <= 3
 
     def _core_cfg(self):
         """(grad steps, solver id) if matricize→NMF→inverse can run as the fused channels-first
@@ -124,7 +124,7 @@ class FactorizerBlock(nn.Module):
         sid = getattr(mf.solver, "native_id", None)
         if sid is None or not isinstance(mf.init, RandomInit) or mf.solver.factor != (0, 1) or mf.verbose:
             return None
-        G = min(max(mf.num_grad_steps, 0), mf.num_iters)
+        G = mf._clamped_grad_steps()
         geo = f.reshape.geometry
         if tuple(mf.size) != (8, geo.P) or not Fn.nmf_core_supported(geo, mf.rank, mf.num_iters, G):
             return None
@@ -157,7 +157,7 @@ class FactorizerBlock(nn.Module):
                 if core is not None:
                     G, sid = core
                 else:
-                    G, sid = min(max(mf.num_grad_steps, 0), mf.num_iters), mf.solver.native_id
+                    G, sid = mf._clamped_grad_steps(), mf.solver.native_id
                 cfg = dict(geo=f.reshape.geometry, T=mf.num_iters, G=G, solver=sid, nmf_eps=mf.solver.eps,
                            eps1=n1.eps, eps2=n2.eps, core=core is not None)
                 if drop is not None:

@@ -13,6 +13,7 @@
 #pragma once
 #include "fz_common.h"
 #include "nmf_core.h"
+#include "nmf_wide.h"
 
 namespace fz {
 
@@ -602,8 +603,7 @@ struct GnWs {
 inline GnWs gn_layout(int64_t nmat, int M, int64_t N, int R, int T, bool backward, bool acc) {
   GnWs w;
   const int64_t nslab = (N + 255) / 256;  // upper bound: the scalar-column variant (CV = 1) has 256-column slabs
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t at = o; o += (n + 3) / 4 * 4; return at; };
+  WsTake take;
   const int Tn = T > 0 ? T : 1;
   w.uh = take((int64_t)Tn * nmat * M * R);                                  // u_1..u_T
   w.vh = take((backward ? (int64_t)Tn : 2) * nmat * N * R);                 // v_1..v_T (or a ping-pong pair)
@@ -615,7 +615,7 @@ inline GnWs gn_layout(int64_t nmat, int M, int64_t N, int R, int T, bool backwar
   w.ga = take(backward ? nmat * M * R : 0);
   w.gbu = take(backward ? nmat * R * R : 0);
   w.gxacc = take(backward && acc ? nmat * M * N : 0);
-  w.total = o;
+  w.total = take.o;
   return w;
 }
 
@@ -725,20 +725,7 @@ static int gn_backward_t(const GnCall<AT>& c, const GnWs& L, int G, const AT* gy
   return FZ_OK;
 }
 
-// ---- one validated call (the entry points of nmf_global.hip have checked every argument) --------------------------
-struct GnArgs {
-  const void *x, *gy;
-  const float *u0, *v0, *gu, *gv;
-  void *y, *gx;
-  float *u_out, *v_out;
-  int64_t nmat;
-  int M;
-  int64_t N;
-  int R, T, G, solver;
-  float eps;
-  void* ws;
-  fz_stream_t stream;
-};
+// ---- one validated call (wide_fwd_entry / wide_bwd_entry of nmf_wide.h have checked every argument) ----------------
 
 #define FZ_GN_RANKS(CALL, SS)                                                                        \
   switch (a.R) {                                                                                     \
@@ -757,7 +744,7 @@ struct GnArgs {
   } while (0)
 
 template <class AT>
-static int gn_run_fwd(const GnArgs& a) {
+static int gn_run_fwd(const WideArgs& a) {
   const GnWs L = gn_layout(a.nmat, a.M, a.N, a.R, a.T, false, false);
   const GnCall<AT> c{(const AT*)a.x, a.u0, a.v0, a.nmat, a.M, a.N, a.R, a.T, a.solver, a.eps, (float*)a.ws,
                      (hipStream_t)a.stream, gn_min(gn_align(a.x), gn_align(a.y))};
@@ -767,7 +754,7 @@ static int gn_run_fwd(const GnArgs& a) {
 }
 
 template <class AT>
-static int gn_run_bwd(const GnArgs& a) {
+static int gn_run_bwd(const WideArgs& a) {
   const GnWs L = gn_layout(a.nmat, a.M, a.N, a.R, a.T, true, sizeof(AT) != sizeof(float));
   const GnCall<AT> c{(const AT*)a.x, a.u0, a.v0, a.nmat, a.M, a.N, a.R, a.T, a.solver, a.eps, (float*)a.ws,
                      (hipStream_t)a.stream, gn_min(gn_align(a.x), gn_min(gn_align(a.gy), gn_align(a.gx)))};
@@ -779,7 +766,7 @@ static int gn_run_bwd(const GnArgs& a) {
 #undef FZ_GN_RANKS
 
 // the bf16 instances (nmf_global_bf16.hip)
-int gn_fwd_bf16(const GnArgs& a);
-int gn_bwd_bf16(const GnArgs& a);
+int gn_fwd_bf16(const WideArgs& a);
+int gn_bwd_bf16(const WideArgs& a);
 
 }  // namespace fz

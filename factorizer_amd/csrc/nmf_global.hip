@@ -25,8 +25,9 @@
 // local parts (V-update undo, gX, gV) in gn_bwd_kernel, the M x R parts (gU, U-update undo) in gn_bwd_u_kernel,
 // with `half_bwd_row` of nmf_core.h — the very code the wave kernels run — for the per-row algebra.
 //
-// The kernels and host paths are in nmf_global.h, templates on the activation storage type; this unit holds the fp32
-// instances and the entry points, nmf_global_bf16.hip the bf16 instances.
+// The kernels and launch sequences are in nmf_global.h, templates on the activation storage type; this unit holds the fp32
+// instances and the entry points, nmf_global_bf16.hip the bf16 instances.  The argument checks of the entry points are those of
+// nmf_wide.h, shared with nmf_global_rank.hip: this family is the descriptor kGn.
 #include "nmf_global.h"
 
 using namespace fz;
@@ -50,72 +51,40 @@ extern "C" int64_t fz_gnmf_workspace_bytes_act(int64_t nmat, int M, int64_t N, i
 
 // number of kernel launches of one call (tests assert it against fz_launch_count)
 extern "C" int fz_gnmf_launches(int T, int Tgrad, int backward) {
-  const int G = Tgrad < 0 ? 0 : (Tgrad > T ? T : Tgrad);
   const int fwd = T == 0 ? 1 : 2 * T + 1;
-  return backward ? fwd + 2 * G + 1 : fwd;
+  return backward ? fwd + 2 * nmf_grad_steps(T, Tgrad) + 1 : fwd;
 }
 
-static int gn_fail(int code, const char* fn, const char* what) { return fail(code, (std::string(fn) + ": " + what).c_str()); }
-
-// `fn`: the entry point named in the error message
-static int gn_fwd_entry(const char* fn, const GnArgs& a, int act_dtype) {
-  if (!fz_gnmf_supported(a.M, a.N, a.R, a.T, a.T)) return gn_fail(FZ_E_UNSUPPORTED, fn, "needs 1 <= M <= 64, 1 <= R <= 4");
-  if (a.solver < FZ_SOLVER_MU || a.solver > FZ_SOLVER_SMU) return gn_fail(FZ_E_ARG, fn, "bad solver");
-  if (act_dtype != FZ_STORE_F32 && act_dtype != FZ_STORE_BF16)
-    return gn_fail(FZ_E_ARG, fn, "act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
-  if (a.nmat < 0 || a.nmat > 65535) return gn_fail(FZ_E_SHAPE, fn, "0 <= nmat <= 65535");
-  if (!a.x || !a.u0 || !a.v0 || !a.y || !a.ws) return gn_fail(FZ_E_ARG, fn, "null pointer");
-  if (a.nmat == 0) return FZ_OK;
-  return act_dtype == FZ_STORE_BF16 ? gn_fwd_bf16(a) : gn_run_fwd<float>(a);
-}
-
-static int gn_bwd_entry(const char* fn, GnArgs a, int Tgrad, int act_dtype) {
-  if (!fz_gnmf_supported(a.M, a.N, a.R, a.T, Tgrad)) return gn_fail(FZ_E_UNSUPPORTED, fn, "needs 1 <= M <= 64, 1 <= R <= 4");
-  if (a.solver < FZ_SOLVER_MU || a.solver > FZ_SOLVER_SMU) return gn_fail(FZ_E_ARG, fn, "bad solver");
-  if (act_dtype != FZ_STORE_F32 && act_dtype != FZ_STORE_BF16)
-    return gn_fail(FZ_E_ARG, fn, "act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
-  if (a.nmat < 0 || a.nmat > 65535) return gn_fail(FZ_E_SHAPE, fn, "0 <= nmat <= 65535");
-  if (!a.x || !a.u0 || !a.v0 || !a.gx || !a.ws || (!a.gy && !a.gu && !a.gv)) return gn_fail(FZ_E_ARG, fn, "null pointer");
-  a.G = Tgrad < 0 ? 0 : (Tgrad > a.T ? a.T : Tgrad);
-  if (a.G < 1) return gn_fail(FZ_E_ARG, fn, "no iteration carries gradient (the caller returns zeros)");
-  if (a.nmat == 0) return FZ_OK;
-  return act_dtype == FZ_STORE_BF16 ? gn_bwd_bf16(a) : gn_run_bwd<float>(a);
-}
-
-static GnArgs gn_fwd_args(const void* x, const float* u0, const float* v0, void* y, float* u_out, float* v_out, int64_t nmat,
-                          int M, int64_t N, int R, int T, int solver, float eps, void* workspace, fz_stream_t stream) {
-  return GnArgs{x, nullptr, u0, v0, nullptr, nullptr, y, nullptr, u_out, v_out, nmat, M, N, R, T, 0, solver, eps, workspace, stream};
-}
-static GnArgs gn_bwd_args(const void* x, const float* u0, const float* v0, const void* gy, const float* gu, const float* gv,
-                          void* gx, int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, void* workspace,
-                          fz_stream_t stream) {
-  return GnArgs{x, gy, u0, v0, gu, gv, nullptr, gx, nullptr, nullptr, nmat, M, N, R, T, 0, solver, eps, workspace, stream};
-}
+static const WideFamily kGn{fz_gnmf_supported,
+                            [](int solver) { return solver >= FZ_SOLVER_MU && solver <= FZ_SOLVER_SMU; },
+                            "needs 1 <= M <= 64, 1 <= R <= 4",
+                            "bad solver",
+                            {{gn_run_fwd<float>, gn_fwd_bf16}, {gn_run_bwd<float>, gn_bwd_bf16}}};
 
 extern "C" int fz_gnmf_fwd_act(const void* x, const float* u0, const float* v0, void* y, float* u_out, float* v_out,
                                int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, int act_dtype,
                                void* workspace, fz_stream_t stream) {
-  return gn_fwd_entry("fz_gnmf_fwd_act", gn_fwd_args(x, u0, v0, y, u_out, v_out, nmat, M, N, R, T, solver, eps, workspace, stream),
-                      act_dtype);
+  return wide_fwd_entry("fz_gnmf_fwd_act", kGn,
+                        wide_fwd_args(x, u0, v0, y, u_out, v_out, nmat, M, N, R, T, solver, eps, workspace, stream), act_dtype);
 }
 
 extern "C" int fz_gnmf_bwd_act(const void* x, const float* u0, const float* v0, const void* gy, const float* gu,
                                const float* gv, void* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad, int solver,
                                float eps, int act_dtype, void* workspace, fz_stream_t stream) {
-  return gn_bwd_entry("fz_gnmf_bwd_act", gn_bwd_args(x, u0, v0, gy, gu, gv, gx, nmat, M, N, R, T, solver, eps, workspace, stream),
-                      Tgrad, act_dtype);
+  return wide_bwd_entry("fz_gnmf_bwd_act", kGn,
+                        wide_bwd_args(x, u0, v0, gy, gu, gv, gx, nmat, M, N, R, T, solver, eps, workspace, stream), Tgrad, act_dtype);
 }
 
 extern "C" int fz_gnmf_fwd(const float* x, const float* u0, const float* v0, float* y, float* u_out, float* v_out,
                            int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, void* workspace,
                            fz_stream_t stream) {
-  return gn_fwd_entry("fz_gnmf_fwd", gn_fwd_args(x, u0, v0, y, u_out, v_out, nmat, M, N, R, T, solver, eps, workspace, stream),
-                      FZ_STORE_F32);
+  return wide_fwd_entry("fz_gnmf_fwd", kGn,
+                        wide_fwd_args(x, u0, v0, y, u_out, v_out, nmat, M, N, R, T, solver, eps, workspace, stream), FZ_STORE_F32);
 }
 
 extern "C" int fz_gnmf_bwd(const float* x, const float* u0, const float* v0, const float* gy, const float* gu,
                            const float* gv, float* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad,
                            int solver, float eps, void* workspace, fz_stream_t stream) {
-  return gn_bwd_entry("fz_gnmf_bwd", gn_bwd_args(x, u0, v0, gy, gu, gv, gx, nmat, M, N, R, T, solver, eps, workspace, stream),
-                      Tgrad, FZ_STORE_F32);
+  return wide_bwd_entry("fz_gnmf_bwd", kGn,
+                        wide_bwd_args(x, u0, v0, gy, gu, gv, gx, nmat, M, N, R, T, solver, eps, workspace, stream), Tgrad, FZ_STORE_F32);
 }

@@ -3,6 +3,6 @@
 #include "nmf_global.h"
 
 namespace fz {
-int gn_fwd_bf16(const GnArgs& a) { return gn_run_fwd<bf16>(a); }
-int gn_bwd_bf16(const GnArgs& a) { return gn_run_bwd<bf16>(a); }
+int gn_fwd_bf16(const WideArgs& a) { return gn_run_fwd<bf16>(a); }
+int gn_bwd_bf16(const WideArgs& a) { return gn_run_bwd<bf16>(a); }
 }  // namespace fz

@@ -14,6 +14,7 @@
 #pragma once
 #include "fz_common.h"
 #include "nmf_core.h"
+#include "nmf_wide.h"
 
 namespace fz {
 
@@ -739,8 +740,7 @@ inline int gx_nslab(int64_t N) { return (int)((N + kGxSlab - 1) / kGxSlab); }
 // acc: the fp32 running sum of gX that a backward on 16-bit activations needs (last, so nothing else moves)
 inline GxWs gx_layout(int64_t nmat, int M, int64_t N, int R, int T, bool backward, bool acc) {
   GxWs w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t at = o; o += (n + 3) / 4 * 4; return at; };
+  WsTake take;
   const int Tn = T > 0 ? T : 1;
   const int64_t MR = (int64_t)M * R, NR = N * R, RQ = (int64_t)R * R;
   w.uh = take((int64_t)Tn * nmat * MR);                       // u_1..u_T
@@ -756,7 +756,7 @@ inline GxWs gx_layout(int64_t nmat, int M, int64_t N, int R, int T, bool backwar
   w.ga = take(backward ? nmat * MR : 0);
   w.gbu = take(backward ? nmat * RQ : 0);
   w.gxacc = take(backward && acc ? nmat * (int64_t)M * N : 0);
-  w.total = o;
+  w.total = take.o;
   return w;
 }
 
@@ -935,20 +935,7 @@ static int gx_backward_t(const GxCall<AT>& c, const GxWs& L, int G, const AT* gy
   return FZ_OK;
 }
 
-// ---- one validated call (the entry points of nmf_global_rank.hip have checked every argument) -----------------------
-struct GxArgs {
-  const void *x, *gy;
-  const float *u0, *v0, *gu, *gv;
-  void *y, *gx;
-  float *u_out, *v_out;
-  int64_t nmat;
-  int M;
-  int64_t N;
-  int R, T, G, solver;
-  float eps;
-  void* ws;
-  fz_stream_t stream;
-};
+// ---- one validated call (wide_fwd_entry / wide_bwd_entry of nmf_wide.h have checked every argument) -------------------
 
 #define FZ_GX_RANKS(CALL, SS)                  \
   do {                                         \
@@ -959,7 +946,7 @@ struct GxArgs {
   } while (0)
 
 template <class AT>
-static int gx_run_fwd(const GxArgs& a) {
+static int gx_run_fwd(const WideArgs& a) {
   const GxWs L = gx_layout(a.nmat, a.M, a.N, a.R, a.T, false, false);
   const GxCall<AT> c{(const AT*)a.x, a.u0, a.v0, a.nmat, a.M, a.N, a.R, a.T, a.eps, (float*)a.ws, (hipStream_t)a.stream,
                      gx_pair(a.x, a.N)};
@@ -970,7 +957,7 @@ static int gx_run_fwd(const GxArgs& a) {
 }
 
 template <class AT>
-static int gx_run_bwd(const GxArgs& a) {
+static int gx_run_bwd(const WideArgs& a) {
   const GxWs L = gx_layout(a.nmat, a.M, a.N, a.R, a.T, true, sizeof(AT) != sizeof(float));
   const GxCall<AT> c{(const AT*)a.x, a.u0, a.v0, a.nmat, a.M, a.N, a.R, a.T, a.eps, (float*)a.ws, (hipStream_t)a.stream,
                      gx_pair(a.x, a.N) & gx_pair(a.gy, a.N)};
@@ -982,7 +969,7 @@ static int gx_run_bwd(const GxArgs& a) {
 #undef FZ_GX_RANKS
 
 // the bf16 instances (nmf_global_rank_bf16.hip)
-int gx_fwd_bf16(const GxArgs& a);
-int gx_bwd_bf16(const GxArgs& a);
+int gx_fwd_bf16(const WideArgs& a);
+int gx_bwd_bf16(const WideArgs& a);
 
 }  // namespace fz

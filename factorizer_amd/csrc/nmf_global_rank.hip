@@ -22,8 +22,9 @@
 // diagonal, -(Woldᵀ·Gnum) below) and goes through gx_prod_kernel like A and B.  No float atomics; every cross-workgroup
 // sum is two-stage in a fixed order, so results replay bit for bit and do not depend on the rest of the batch.
 //
-// The kernels and host paths are in nmf_global_rank.h, templates on the activation storage type; this unit holds the fp32
-// instances and the entry points, nmf_global_rank_bf16.hip the bf16 instances.
+// The kernels and launch sequences are in nmf_global_rank.h, templates on the activation storage type; this unit holds the fp32
+// instances and the entry points, nmf_global_rank_bf16.hip the bf16 instances.  The argument checks of the entry points are those
+// of nmf_wide.h, shared with nmf_global.hip: this family is the descriptor kGx.
 #include "nmf_global_rank.h"
 
 using namespace fz;
@@ -49,74 +50,40 @@ extern "C" int64_t fz_gnmfx_workspace_bytes_act(int64_t nmat, int M, int64_t N, 
 // number of kernel launches of one call (tests assert it against fz_launch_count)
 extern "C" int fz_gnmfx_launches(int M, int64_t N, int R, int T, int Tgrad, int backward) {
   (void)M; (void)N; (void)R;
-  const int G = Tgrad < 0 ? 0 : (Tgrad > T ? T : Tgrad);
   const int fwd = T == 0 ? 1 : 3 * T;
-  return backward ? fwd + 3 * G + 1 : fwd;
+  return backward ? fwd + 3 * nmf_grad_steps(T, Tgrad) + 1 : fwd;
 }
 
-static int gx_fail(int code, const char* fn, const char* what) { return fail(code, (std::string(fn) + ": " + what).c_str()); }
-
-// `fn`: the entry point named in the error message
-static int gx_fwd_entry(const char* fn, const GxArgs& a, int act_dtype) {
-  if (!fz_gnmfx_supported(a.M, a.N, a.R, a.T, a.T))
-    return gx_fail(FZ_E_UNSUPPORTED, fn, "needs 16 <= M <= 512, 1 <= R <= min(32, M), and R > 4 or M > 64");
-  if (a.solver != FZ_SOLVER_MU && a.solver != FZ_SOLVER_HALS) return gx_fail(FZ_E_ARG, fn, "solver must be MU or HALS");
-  if (act_dtype != FZ_STORE_F32 && act_dtype != FZ_STORE_BF16)
-    return gx_fail(FZ_E_ARG, fn, "act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
-  if (a.nmat < 0 || a.nmat > 65535) return gx_fail(FZ_E_SHAPE, fn, "0 <= nmat <= 65535");
-  if (!a.x || !a.u0 || !a.v0 || !a.y || !a.ws) return gx_fail(FZ_E_ARG, fn, "null pointer");
-  if (a.nmat == 0) return FZ_OK;
-  return act_dtype == FZ_STORE_BF16 ? gx_fwd_bf16(a) : gx_run_fwd<float>(a);
-}
-
-static int gx_bwd_entry(const char* fn, GxArgs a, int Tgrad, int act_dtype) {
-  if (!fz_gnmfx_supported(a.M, a.N, a.R, a.T, Tgrad))
-    return gx_fail(FZ_E_UNSUPPORTED, fn, "needs 16 <= M <= 512, 1 <= R <= min(32, M), and R > 4 or M > 64");
-  if (a.solver != FZ_SOLVER_MU && a.solver != FZ_SOLVER_HALS) return gx_fail(FZ_E_ARG, fn, "solver must be MU or HALS");
-  if (act_dtype != FZ_STORE_F32 && act_dtype != FZ_STORE_BF16)
-    return gx_fail(FZ_E_ARG, fn, "act_dtype must be FZ_STORE_F32 or FZ_STORE_BF16");
-  if (a.nmat < 0 || a.nmat > 65535) return gx_fail(FZ_E_SHAPE, fn, "0 <= nmat <= 65535");
-  if (!a.x || !a.u0 || !a.v0 || !a.gx || !a.ws || (!a.gy && !a.gu && !a.gv)) return gx_fail(FZ_E_ARG, fn, "null pointer");
-  a.G = Tgrad < 0 ? 0 : (Tgrad > a.T ? a.T : Tgrad);
-  if (a.G < 1) return gx_fail(FZ_E_ARG, fn, "no iteration carries gradient (the caller returns zeros)");
-  if (a.nmat == 0) return FZ_OK;
-  return act_dtype == FZ_STORE_BF16 ? gx_bwd_bf16(a) : gx_run_bwd<float>(a);
-}
-
-static GxArgs gx_fwd_args(const void* x, const float* u0, const float* v0, void* y, float* u_out, float* v_out, int64_t nmat,
-                          int M, int64_t N, int R, int T, int solver, float eps, void* workspace, fz_stream_t stream) {
-  return GxArgs{x, nullptr, u0, v0, nullptr, nullptr, y, nullptr, u_out, v_out, nmat, M, N, R, T, 0, solver, eps, workspace, stream};
-}
-static GxArgs gx_bwd_args(const void* x, const float* u0, const float* v0, const void* gy, const float* gu, const float* gv,
-                          void* gx, int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, void* workspace,
-                          fz_stream_t stream) {
-  return GxArgs{x, gy, u0, v0, gu, gv, nullptr, gx, nullptr, nullptr, nmat, M, N, R, T, 0, solver, eps, workspace, stream};
-}
+static const WideFamily kGx{fz_gnmfx_supported,
+                            [](int solver) { return solver == FZ_SOLVER_MU || solver == FZ_SOLVER_HALS; },
+                            "needs 16 <= M <= 512, 1 <= R <= min(32, M), and R > 4 or M > 64",
+                            "solver must be MU or HALS",
+                            {{gx_run_fwd<float>, gx_fwd_bf16}, {gx_run_bwd<float>, gx_bwd_bf16}}};
 
 extern "C" int fz_gnmfx_fwd_act(const void* x, const float* u0, const float* v0, void* y, float* u_out, float* v_out,
                                 int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, int act_dtype,
                                 void* workspace, fz_stream_t stream) {
-  return gx_fwd_entry("fz_gnmfx_fwd_act", gx_fwd_args(x, u0, v0, y, u_out, v_out, nmat, M, N, R, T, solver, eps, workspace, stream),
-                      act_dtype);
+  return wide_fwd_entry("fz_gnmfx_fwd_act", kGx,
+                        wide_fwd_args(x, u0, v0, y, u_out, v_out, nmat, M, N, R, T, solver, eps, workspace, stream), act_dtype);
 }
 
 extern "C" int fz_gnmfx_bwd_act(const void* x, const float* u0, const float* v0, const void* gy, const float* gu,
                                 const float* gv, void* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad, int solver,
                                 float eps, int act_dtype, void* workspace, fz_stream_t stream) {
-  return gx_bwd_entry("fz_gnmfx_bwd_act", gx_bwd_args(x, u0, v0, gy, gu, gv, gx, nmat, M, N, R, T, solver, eps, workspace, stream),
-                      Tgrad, act_dtype);
+  return wide_bwd_entry("fz_gnmfx_bwd_act", kGx,
+                        wide_bwd_args(x, u0, v0, gy, gu, gv, gx, nmat, M, N, R, T, solver, eps, workspace, stream), Tgrad, act_dtype);
 }
 
 extern "C" int fz_gnmfx_fwd(const float* x, const float* u0, const float* v0, float* y, float* u_out, float* v_out,
                             int64_t nmat, int M, int64_t N, int R, int T, int solver, float eps, void* workspace,
                             fz_stream_t stream) {
-  return gx_fwd_entry("fz_gnmfx_fwd", gx_fwd_args(x, u0, v0, y, u_out, v_out, nmat, M, N, R, T, solver, eps, workspace, stream),
-                      FZ_STORE_F32);
+  return wide_fwd_entry("fz_gnmfx_fwd", kGx,
+                        wide_fwd_args(x, u0, v0, y, u_out, v_out, nmat, M, N, R, T, solver, eps, workspace, stream), FZ_STORE_F32);
 }
 
 extern "C" int fz_gnmfx_bwd(const float* x, const float* u0, const float* v0, const float* gy, const float* gu,
                             const float* gv, float* gx, int64_t nmat, int M, int64_t N, int R, int T, int Tgrad,
                             int solver, float eps, void* workspace, fz_stream_t stream) {
-  return gx_bwd_entry("fz_gnmfx_bwd", gx_bwd_args(x, u0, v0, gy, gu, gv, gx, nmat, M, N, R, T, solver, eps, workspace, stream),
-                      Tgrad, FZ_STORE_F32);
+  return wide_bwd_entry("fz_gnmfx_bwd", kGx,
+                        wide_bwd_args(x, u0, v0, gy, gu, gv, gx, nmat, M, N, R, T, solver, eps, workspace, stream), Tgrad, FZ_STORE_F32);
 }

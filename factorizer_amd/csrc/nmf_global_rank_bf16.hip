@@ -3,6 +3,6 @@
 #include "nmf_global_rank.h"
 
 namespace fz {
-int gx_fwd_bf16(const GxArgs& a) { return gx_run_fwd<bf16>(a); }
-int gx_bwd_bf16(const GxArgs& a) { return gx_run_bwd<bf16>(a); }
+int gx_fwd_bf16(const WideArgs& a) { return gx_run_fwd<bf16>(a); }
+int gx_bwd_bf16(const WideArgs& a) { return gx_run_bwd<bf16>(a); }
 }  // namespace fz

@@ -7,6 +7,7 @@
 // (factorization/matrix_factorization.py:213-227, 241-247, 514-546).
 #include "fz_common.h"
 #include "nmf_core.h"
+#include "nmf_shapes.h"
 
 namespace fz {
 
@@ -185,20 +186,6 @@ __global__ __launch_bounds__(256, (nmf_bwd_waves_per_simd<M, NPL, R>())) void nm
 }
 
 // ---- host launchers for this rank -------------------------------------------------------
-struct NmfArgs {
-  const void *x;            // matrices: FZ_AT
-  const float *u0, *v0;
-  const void *gy;           // FZ_AT
-  const float *gu, *gv;
-  void *y;                  // FZ_AT
-  float *uo, *vo;
-  void *gx;                 // FZ_AT
-  int64_t nmat;
-  int M, N, T, G, solver;
-  float eps;
-  hipStream_t stream;
-};
-
 static constexpr int kMaxLdsBytes = 160 * 1024;
 
 template <int M, int NPL, int SOLVER, bool FAST>
@@ -249,18 +236,12 @@ static int launch_solver(const NmfArgs& a) {
 
 template <bool BWD>
 static int launch_shape(const NmfArgs& a) {
-  // a lane holds NPL columns: the smallest family that holds the matrix (a 8x150 matrix of the
-  // 160x192x160 / patch (5,6,5) configuration in the 8x512 family spends 70 % of its work on padding)
+  // the first row of the shape table (nmf_shapes.h) that holds the matrix; exactly 8x512 has a form without masks
   if (a.M == 8 && a.N == 512) return launch_solver<BWD, 8, 8, true>(a);
-  if (a.M <= 8 && a.N <= 64) return launch_solver<BWD, 8, 1, false>(a);
-  if (a.M <= 8 && a.N <= 128) return launch_solver<BWD, 8, 2, false>(a);
-  if (a.M <= 8 && a.N <= 192) return launch_solver<BWD, 8, 3, false>(a);   // 8x150: patch (5,6,5) of BASELINE configs[4]
-  if (a.M <= 8 && a.N <= 256) return launch_solver<BWD, 8, 4, false>(a);
-  if (a.M <= 8 && a.N <= 512) return launch_solver<BWD, 8, 8, false>(a);
-  if (a.M <= 16 && a.N <= 64) return launch_solver<BWD, 16, 1, false>(a);
-  if (a.M <= 16 && a.N <= 256) return launch_solver<BWD, 16, 4, false>(a);
-  if (a.M <= 32 && a.N <= 64) return launch_solver<BWD, 32, 1, false>(a);
-  if (a.M <= 32 && a.N <= 128) return launch_solver<BWD, 32, 2, false>(a);
+#define FZ_NMF_ROW(MP, NPL, MMAX, NMAX) \
+  if (a.M <= MMAX && a.N <= NMAX) return launch_solver<BWD, MP, NPL, false>(a);
+  FZ_NMF_SHAPES(FZ_NMF_ROW)
+#undef FZ_NMF_ROW
   return fail(FZ_E_UNSUPPORTED, "fz_nmf: (M,N) outside the native kernel families");
 }
 

@@ -171,9 +171,29 @@ def swm_inverse(y, geo):
     return SWMInverseFn.apply(y, geo)
 
 
-# ---- batched NMF --------------------------------------------------------------------------
+# ---- batched NMF: three kernel families behind one binding ----------------------------------------
+# family: (forward entry point, backward entry point, takes a workspace, joins the side streams first)
+#   "nmf"    wave-resident (csrc/nmf.hip): M <= 32, N <= 512, rank <= 4
+#   "gnmf"   split-N, matrices too wide for one wavefront (csrc/nmf_global.hip): M <= 64, rank <= 4
+#   "gnmfx"  split-N (csrc/nmf_global_rank.hip): 16 <= M <= 512, rank <= 32, MU / HALS
+# all three on fp32 or bf16 activation storage, with one argument list but for the workspace
+_NMF_FAMILIES = {
+    "nmf": ("fz_nmf_fwd", "fz_nmf_bwd", False, True),
+    "gnmf": ("fz_gnmf_fwd_act", "fz_gnmf_bwd_act", True, False),
+    "gnmfx": ("fz_gnmfx_fwd_act", "fz_gnmfx_bwd_act", True, False),
+}
+
+
 def nmf_supported(M, N_, R, T, G) -> bool:
     return bool(N.lib().fz_nmf_supported(int(M), int(N_), int(R), int(T), int(G)))
+
+
+def gnmf_supported(M, N_, R, T, G) -> bool:
+    return bool(N.lib().fz_gnmf_supported(int(M), int(N_), int(R), int(T), int(G)))
+
+
+def gnmfx_supported(M, N_, R, T, G) -> bool:
+    return bool(N.lib().fz_gnmfx_supported(int(M), int(N_), int(R), int(T), int(G)))
 
 
 def _join_side_streams(t):
@@ -185,110 +205,6 @@ def _join_side_streams(t):
         _PW.wait_wgrad_streams_all(t.device)
 
 
-def _nmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=False):
-    M, Nn = x.shape[-2:]
-    R = u0.shape[1]
-    nmat = x.numel() // (M * Nn)
-    y = torch.empty_like(x)
-    u = v = None
-    if want_uv:
-        # the factors are fp32 whatever the storage type of x (fp32 U/V/Gram/eps)
-        u = torch.empty((*x.shape[:-2], M, R), dtype=torch.float32, device=x.device)
-        v = torch.empty((*x.shape[:-2], Nn, R), dtype=torch.float32, device=x.device)
-    ad = N.act_dtype(x)
-    with _dev_guard(x):
-        _join_side_streams(x)
-        rc = _timed(f"nmf_fwd_{M}x{Nn}", 2 * x.numel() * x.element_size(), lambda: N.lib().fz_nmf_fwd(
-            x.data_ptr(), u0.data_ptr(), v0.data_ptr(), y.data_ptr(), N.ptr(u), N.ptr(v), nmat, M, Nn, R, T,
-            N.SOLVER_ID[solver], eps, ad, N.stream_ptr(x)))
-    N.check(rc, "fz_nmf_fwd")
-    return y, u, v
-
-
-def _nmf_bwd_raw(x, u0, v0, gy, gu, gv, T, G, solver, eps):
-    M, Nn = x.shape[-2:]
-    R = u0.shape[1]
-    nmat = x.numel() // (M * Nn)
-    gx = torch.empty_like(x)
-    ad = N.act_dtype(x)
-    if gy is not None and gy.dtype != x.dtype:
-        gy = gy.to(x.dtype)
-    if gu is not None:
-        gu, gv = gu.float().contiguous(), gv.float().contiguous()
-    with _dev_guard(x):
-        _join_side_streams(x)
-        rc = _timed(f"nmf_bwd_{M}x{Nn}", 3 * x.numel() * x.element_size(), lambda: N.lib().fz_nmf_bwd(
-            x.data_ptr(), u0.data_ptr(), v0.data_ptr(), N.ptr(gy), N.ptr(gu), N.ptr(gv), gx.data_ptr(), nmat,
-            M, Nn, R, T, G, N.SOLVER_ID[solver], eps, ad, N.stream_ptr(x)))
-    N.check(rc, "fz_nmf_bwd")
-    return gx
-
-
-class NMFFn(torch.autograd.Function):
-    """y = u_T v_Tᵀ after T unrolled iterations (matrix_factorization.py:514-546)."""
-
-    @staticmethod
-    def forward(ctx, x, u0, v0, T, G, solver, eps):
-        x = x.contiguous()
-        u0 = u0.contiguous()
-        v0 = v0.contiguous()
-        y, _, _ = _nmf_fwd_raw(x, u0, v0, T, solver, eps)
-        ctx.save_for_backward(x, u0, v0)
-        ctx.cfg = (T, G, solver, eps)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, u0, v0 = ctx.saved_tensors
-        T, G, solver, eps = ctx.cfg
-        if G <= 0:
-            return torch.zeros_like(x), None, None, None, None, None, None
-        gx = _nmf_bwd_raw(x, u0, v0, gy.contiguous(), None, None, T, G, solver, eps)
-        return gx, None, None, None, None, None, None
-
-
-class NMFDecomposeFn(torch.autograd.Function):
-    """(u_T, v_T) of the same iterations — NMF.decompose (matrix_factorization.py:514-530)."""
-
-    @staticmethod
-    def forward(ctx, x, u0, v0, T, G, solver, eps):
-        x = x.contiguous()
-        u0 = u0.contiguous()
-        v0 = v0.contiguous()
-        _, u, v = _nmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=True)
-        ctx.save_for_backward(x, u0, v0)
-        ctx.cfg = (T, G, solver, eps)
-        return u, v
-
-    @staticmethod
-    def backward(ctx, gu, gv):
-        x, u0, v0 = ctx.saved_tensors
-        T, G, solver, eps = ctx.cfg
-        if G <= 0:
-            return torch.zeros_like(x), None, None, None, None, None, None
-        gx = _nmf_bwd_raw(x, u0, v0, None, gu.contiguous(), gv.contiguous(), T, G, solver, eps)
-        return gx, None, None, None, None, None, None
-
-
-def nmf(x, u0, v0, T, G, solver, eps=1e-16):
-    return NMFFn.apply(x, u0, v0, T, G, solver, eps)
-
-
-def nmf_decompose(x, u0, v0, T, G, solver, eps=1e-16):
-    return NMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps)
-
-
-# ---- split-N NMF: matrices too wide for one wavefront (SURVEY §8 f-3) ----------------------------
-# two kernel families with one argument list: "gnmf" (csrc/nmf_global.hip: M <= 64, rank <= 4) and "gnmfx"
-# (csrc/nmf_global_rank.hip: 16 <= M <= 512, rank <= 32, MU / HALS); fp32 or bf16 activation storage
-def gnmf_supported(M, N_, R, T, G) -> bool:
-    return bool(N.lib().fz_gnmf_supported(int(M), int(N_), int(R), int(T), int(G)))
-
-
-def gnmfx_supported(M, N_, R, T, G) -> bool:
-    return bool(N.lib().fz_gnmfx_supported(int(M), int(N_), int(R), int(T), int(G)))
-
-
 def _gnmf_ws(x, nmat, M, Nn, R, T, backward, fam="gnmf"):
     nb = getattr(N.lib(), f"fz_{fam}_workspace_bytes_act")(nmat, M, Nn, R, T, int(backward), N.act_dtype(x))
     if nb < 0:
@@ -296,54 +212,66 @@ def _gnmf_ws(x, nmat, M, Nn, R, T, backward, fam="gnmf"):
     return torch.empty(max(nb // 4, 1), dtype=torch.float32, device=x.device)
 
 
-def _gnmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=False, fam="gnmf"):
-    """x fp32 or bf16 storage; y has the dtype of x, the factors are always fp32 (as _nmf_fwd_raw returns them)"""
+def _nmf_launch(fam, backward, x, R, T, head, tail):
+    """one entry point of `fam`: (*head, nmat, M, N, R, T, *tail, act_dtype, [workspace,] stream)"""
+    fwd_name, bwd_name, has_ws, join = _NMF_FAMILIES[fam]
+    name = bwd_name if backward else fwd_name
+    M, Nn = x.shape[-2:]
+    nmat = x.numel() // (M * Nn)
+    ws = _gnmf_ws(x, nmat, M, Nn, R, T, backward, fam) if has_ws else None
+    entry = getattr(N.lib(), name)
+    args = (*head, nmat, M, Nn, R, T, *tail, N.act_dtype(x), *(() if ws is None else (ws.data_ptr(),)), N.stream_ptr(x))
+    with _dev_guard(x):
+        if join:
+            _join_side_streams(x)
+        rc = _timed(f"{fam}_{'bwd' if backward else 'fwd'}_{M}x{Nn}", (3 if backward else 2) * x.numel() * x.element_size(),
+                    lambda: entry(*args))
+    N.check(rc, name)
+
+
+def _nmf_fwd(fam, x, u0, v0, T, solver, eps, want_uv=False):
+    """x fp32 or bf16 storage; y has the dtype of x, the factors are fp32 whatever the storage type of x (SURVEY.md §5:
+    fp32 U/V/Gram/eps)"""
     M, Nn = x.shape[-2:]
     R = u0.shape[1]
-    nmat = x.numel() // (M * Nn)
     y = torch.empty_like(x)
     u = v = None
     if want_uv:
         u = torch.empty((*x.shape[:-2], M, R), dtype=torch.float32, device=x.device)
         v = torch.empty((*x.shape[:-2], Nn, R), dtype=torch.float32, device=x.device)
-    ws = _gnmf_ws(x, nmat, M, Nn, R, T, False, fam)
-    fwd = getattr(N.lib(), f"fz_{fam}_fwd_act")
-    ad = N.act_dtype(x)
-    with _dev_guard(x):
-        rc = _timed(f"{fam}_fwd_{M}x{Nn}", 2 * x.numel() * x.element_size(), lambda: fwd(
-            x.data_ptr(), u0.data_ptr(), v0.data_ptr(), y.data_ptr(), N.ptr(u), N.ptr(v), nmat, M, Nn, R, T,
-            N.SOLVER_ID[solver], eps, ad, ws.data_ptr(), N.stream_ptr(x)))
-    N.check(rc, f"fz_{fam}_fwd_act")
+    _nmf_launch(fam, False, x, R, T, (x.data_ptr(), u0.data_ptr(), v0.data_ptr(), y.data_ptr(), N.ptr(u), N.ptr(v)),
+                (N.SOLVER_ID[solver], eps))
     return y, u, v
 
 
-def _gnmf_bwd_raw(x, u0, v0, gy, gu, gv, T, G, solver, eps, fam="gnmf"):
-    M, Nn = x.shape[-2:]
-    R = u0.shape[1]
-    nmat = x.numel() // (M * Nn)
+def _nmf_bwd(fam, x, u0, v0, gy, gu, gv, T, G, solver, eps):
     gx = torch.empty_like(x)
     if gy is not None and gy.dtype != x.dtype:
         gy = gy.to(x.dtype)
     if gu is not None:
         gu, gv = gu.float().contiguous(), gv.float().contiguous()
-    ws = _gnmf_ws(x, nmat, M, Nn, R, T, True, fam)
-    bwd = getattr(N.lib(), f"fz_{fam}_bwd_act")
-    ad = N.act_dtype(x)
-    with _dev_guard(x):
-        rc = _timed(f"{fam}_bwd_{M}x{Nn}", 3 * x.numel() * x.element_size(), lambda: bwd(
-            x.data_ptr(), u0.data_ptr(), v0.data_ptr(), N.ptr(gy), N.ptr(gu), N.ptr(gv), gx.data_ptr(), nmat, M, Nn,
-            R, T, G, N.SOLVER_ID[solver], eps, ad, ws.data_ptr(), N.stream_ptr(x)))
-    N.check(rc, f"fz_{fam}_bwd_act")
+    _nmf_launch(fam, True, x, u0.shape[1], T,
+                (x.data_ptr(), u0.data_ptr(), v0.data_ptr(), N.ptr(gy), N.ptr(gu), N.ptr(gv), gx.data_ptr()),
+                (G, N.SOLVER_ID[solver], eps))
     return gx
 
 
-class GNMFFn(torch.autograd.Function):
-    """y = u_T v_Tᵀ for matrices whose columns are split over workgroups (`fam`: the kernel family)."""
+# the wave-resident family by name: the block's hand-chained node calls these (pointwise.py)
+def _nmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=False):
+    return _nmf_fwd("nmf", x, u0, v0, T, solver, eps, want_uv)
+
+
+def _nmf_bwd_raw(x, u0, v0, gy, gu, gv, T, G, solver, eps):
+    return _nmf_bwd("nmf", x, u0, v0, gy, gu, gv, T, G, solver, eps)
+
+
+class NMFFn(torch.autograd.Function):
+    """y = u_T v_Tᵀ after T unrolled iterations (matrix_factorization.py:514-546); `fam`: the kernel family."""
 
     @staticmethod
     def forward(ctx, x, u0, v0, T, G, solver, eps, fam):
         x, u0, v0 = x.contiguous(), u0.contiguous(), v0.contiguous()
-        y, _, _ = _gnmf_fwd_raw(x, u0, v0, T, solver, eps, fam=fam)
+        y, _, _ = _nmf_fwd(fam, x, u0, v0, T, solver, eps)
         ctx.save_for_backward(x, u0, v0)
         ctx.cfg = (T, G, solver, eps, fam)
         return y
@@ -354,14 +282,16 @@ class GNMFFn(torch.autograd.Function):
         T, G, solver, eps, fam = ctx.cfg
         if G <= 0:
             return (torch.zeros_like(x), *[None] * 7)
-        return (_gnmf_bwd_raw(x, u0, v0, gy.contiguous(), None, None, T, G, solver, eps, fam), *[None] * 7)
+        return (_nmf_bwd(fam, x, u0, v0, gy.contiguous(), None, None, T, G, solver, eps), *[None] * 7)
 
 
-class GNMFDecomposeFn(torch.autograd.Function):
+class NMFDecomposeFn(torch.autograd.Function):
+    """(u_T, v_T) of the same iterations — NMF.decompose (matrix_factorization.py:514-530)."""
+
     @staticmethod
     def forward(ctx, x, u0, v0, T, G, solver, eps, fam):
         x, u0, v0 = x.contiguous(), u0.contiguous(), v0.contiguous()
-        _, u, v = _gnmf_fwd_raw(x, u0, v0, T, solver, eps, want_uv=True, fam=fam)
+        _, u, v = _nmf_fwd(fam, x, u0, v0, T, solver, eps, want_uv=True)
         ctx.save_for_backward(x, u0, v0)
         ctx.cfg = (T, G, solver, eps, fam)
         return u, v
@@ -372,24 +302,32 @@ class GNMFDecomposeFn(torch.autograd.Function):
         T, G, solver, eps, fam = ctx.cfg
         if G <= 0:
             return (torch.zeros_like(x), *[None] * 7)
-        gx = _gnmf_bwd_raw(x, u0, v0, None, gu.contiguous(), gv.contiguous(), T, G, solver, eps, fam)
+        gx = _nmf_bwd(fam, x, u0, v0, None, gu.contiguous(), gv.contiguous(), T, G, solver, eps)
         return (gx, *[None] * 7)
 
 
+def nmf(x, u0, v0, T, G, solver, eps=1e-16):
+    return NMFFn.apply(x, u0, v0, T, G, solver, eps, "nmf")
+
+
+def nmf_decompose(x, u0, v0, T, G, solver, eps=1e-16):
+    return NMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps, "nmf")
+
+
 def gnmf(x, u0, v0, T, G, solver, eps=1e-16):
-    return GNMFFn.apply(x, u0, v0, T, G, solver, eps, "gnmf")
+    return NMFFn.apply(x, u0, v0, T, G, solver, eps, "gnmf")
 
 
 def gnmf_decompose(x, u0, v0, T, G, solver, eps=1e-16):
-    return GNMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps, "gnmf")
+    return NMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps, "gnmf")
 
 
 def gnmfx(x, u0, v0, T, G, solver, eps=1e-16):
-    return GNMFFn.apply(x, u0, v0, T, G, solver, eps, "gnmfx")
+    return NMFFn.apply(x, u0, v0, T, G, solver, eps, "gnmfx")
 
 
 def gnmfx_decompose(x, u0, v0, T, G, solver, eps=1e-16):
-    return GNMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps, "gnmfx")
+    return NMFDecomposeFn.apply(x, u0, v0, T, G, solver, eps, "gnmfx")
 
 
 # ---- fused FactMixer core on channels-first tensors ------------------------------------------

@@ -413,44 +413,45 @@ class MatrixFactorization(nn.Module):
         self._wide = False
 
     # -- which path -------------------------------------------------------------------
+    def _clamped_grad_steps(self):
+        return min(max(self.num_grad_steps, 0), self.num_iters)
+
     def _native_solver(self, x: Tensor):
-        """Solver id if this call is covered by the gfx950 kernels, else None; `self._wide` then says which
-        family: the wave-resident kernels (False) or a split-N family for wide matrices ("gnmf": M <= 64, rank <= 4;
-        "gnmfx": M <= 512, rank <= 32, MU / HALS)."""
+        """(solver id, kernel family) if this call is covered by the gfx950 kernels, else (None, None).  The family: "nmf",
+        the wave-resident kernels, or a split-N family for wide matrices ("gnmf": M <= 64, rank <= 4; "gnmfx": M <= 512,
+        rank <= 32, MU / HALS).  `self._wide` keeps a record of the last plan (False, "gnmf" or "gnmfx") for tests and
+        probes; nothing in the package reads it."""
         self._wide = False
         if not x.is_cuda or self.verbose or not x.numel():
-            return None
+            return None, None
         sid = getattr(self.solver, "native_id", None)
         if sid is None or not isinstance(self.init, RandomInit) or self.solver.factor != (0, 1):
-            return None
+            return None, None
         # float32, or bfloat16 STORAGE: the kernels then load/store bf16 and factorise in fp32
         # (u0 / v0 stay the fp32 buffers; SURVEY.md §5, eps at matrix_factorization.py:200,236)
         if x.dtype not in (torch.float32, torch.bfloat16) or tuple(x.shape[-2:]) != self.size:
-            return None
+            return None, None
         if self.init.u0.dtype != torch.float32:
-            return None
-        G = min(max(self.num_grad_steps, 0), self.num_iters)
-        if not Fn.nmf_supported(self.size[0], self.size[1], self.rank, self.num_iters, G):
-            # wider than one wavefront can hold (global Matricize, num_heads= forms): the split-N kernels
-            # (fp32 or bf16 storage, as the wave-resident kernels)
-            if x.numel() // (self.size[0] * self.size[1]) <= 65535:
-                if Fn.gnmf_supported(self.size[0], self.size[1], self.rank, self.num_iters, G):
-                    self._wide = "gnmf"
-                    return sid
-                # ranks up to 32, up to 512 rows (rank=None of the default-constructed model): MU and HALS only
-                if sid in ("mu", "hals") and Fn.gnmfx_supported(self.size[0], self.size[1], self.rank, self.num_iters, G):
-                    self._wide = "gnmfx"
-                    return sid
-            composed.warn_once(
-                f"nmf{self.size}{self.rank}",
-                f"NMF size={self.size} rank={self.rank} is outside the native kernel families; "
-                "using the composed PyTorch path on device")
-            return None
-        return sid
+            return None, None
+        shape = (self.size[0], self.size[1], self.rank, self.num_iters, self._clamped_grad_steps())
+        if Fn.nmf_supported(*shape):
+            return sid, "nmf"
+        # wider than one wavefront can hold (global Matricize, num_heads= forms): the split-N kernels (fp32 or bf16 storage,
+        # as the wave-resident kernels); "gnmfx" — ranks up to 32, up to 512 rows (rank=None of the default-constructed
+        # model) — has MU and HALS only
+        if x.numel() // (self.size[0] * self.size[1]) <= 65535:
+            for fam, solvers in (("gnmf", ("mu", "hals", "cd", "smu")), ("gnmfx", ("mu", "hals"))):
+                if sid in solvers and getattr(Fn, fam + "_supported")(*shape):
+                    self._wide = fam
+                    return sid, fam
+        composed.warn_once(
+            f"nmf{self.size}{self.rank}",
+            f"NMF size={self.size} rank={self.rank} is outside the native kernel families; "
+            "using the composed PyTorch path on device")
+        return None, None
 
     def _grad_steps(self, x):
-        G = min(max(self.num_grad_steps, 0), self.num_iters)
-        return G if (torch.is_grad_enabled() and x.requires_grad) else 0
+        return self._clamped_grad_steps() if (torch.is_grad_enabled() and x.requires_grad) else 0
 
     def context(self, it: int):
         return torch.no_grad() if it < self.num_iters - self.num_grad_steps + 1 else nullcontext()
@@ -458,11 +459,11 @@ class MatrixFactorization(nn.Module):
     # -- API --------------------------------------------------------------------------
     def decompose(self, x: Tensor, *args, **kwargs):
         x = x.as_subclass(Tensor)
-        sid = self._native_solver(x) if not args and not kwargs else None   # (extra solver arguments — wmu's weights — : composed)
+        # (extra solver arguments — wmu's weights — : composed)
+        sid, fam = self._native_solver(x) if not args and not kwargs else (None, None)
         if sid is not None:
-            fn = {False: Fn.nmf_decompose, "gnmf": Fn.gnmf_decompose, "gnmfx": Fn.gnmfx_decompose}[self._wide]
-            return fn(x, self.init.u0, self.init.v0, self.num_iters,
-                      min(max(self.num_grad_steps, 0), self.num_iters), sid, self.solver.eps)
+            return getattr(Fn, fam + "_decompose")(x, self.init.u0, self.init.v0, self.num_iters, self._clamped_grad_steps(),
+                                                   sid, self.solver.eps)
         if x.dtype in (torch.bfloat16, torch.float16):
             # composed path in reduced precision: factorise in fp32 (eps = 1e-16 vanishes in fp16 and the
             # Gram matrices lose their low bits in bf16), factors are returned in fp32
@@ -485,11 +486,10 @@ class MatrixFactorization(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         x = x.as_subclass(Tensor)
-        sid = self._native_solver(x)
+        sid, fam = self._native_solver(x)
         if sid is not None:
-            fn = {False: Fn.nmf, "gnmf": Fn.gnmf, "gnmfx": Fn.gnmfx}[self._wide]
-            return fn(x, self.init.u0, self.init.v0, self.num_iters,
-                      min(max(self.num_grad_steps, 0), self.num_iters), sid, self.solver.eps)
+            return getattr(Fn, fam)(x, self.init.u0, self.init.v0, self.num_iters, self._clamped_grad_steps(), sid,
+                                    self.solver.eps)
         u, v = self.decompose(x)
         return self.reconstruct(u, v).to(x.dtype)
 

@@ -47,18 +47,25 @@ def _mf(M, N, R, T, G, solver, u0, v0):
     return mf.to(DEV)
 
 
-def _check_standalone(name, x, u0, v0, T, G, solver, gy):
+def _check_standalone(name, x, u0, v0, T, G, solver, gy, guards=None):
+    """`guards`: a list that receives (what, the guard, the bound of P.close without the guard) of every comparison"""
     M, N = x.shape[-2:]
     R = u0.shape[1]
     mf = _mf(M, N, R, T, G, solver, u0, v0)
+
+    def close(what, got, ref64, ref32):
+        if guards is not None:
+            guards.append((what, _kink(ref32, ref64), 1e-4 * ref64.float().abs().max().item() + 1e-6))
+        P.close(f"{name}: {what}", got, ref64, extra=_kink(ref32, ref64))
+
     y64, u64, v64, gx64 = composed(x, u0, v0, T, G, solver, gy=gy)
     y32, u32, v32, gx32 = composed(x, u0, v0, T, G, solver, gy=gy, dtype=torch.float32)
     xd = x.to(DEV).requires_grad_(True)
     with Launches():
         y = mf(xd)
         (gx,) = torch.autograd.grad(y, xd, gy.to(DEV))
-    P.close(f"{name}: y", y, y64, extra=_kink(y32, y64))
-    P.close(f"{name}: gx", gx, gx64, extra=_kink(gx32, gx64))
+    close("y", y, y64, y32)
+    close("gx", gx, gx64, gx32)
     # decompose(): u and v, with gradients into both
     gu, gv = torch.rand_like(u64.float()) - 0.5, torch.rand_like(v64.float()) - 0.5
     _, _, _, gxd64 = composed(x, u0, v0, T, G, solver, gu=gu, gv=gv)
@@ -67,9 +74,9 @@ def _check_standalone(name, x, u0, v0, T, G, solver, gy):
     with Launches():
         u, v = mf.decompose(xd)
         (gxd,) = torch.autograd.grad([u, v], xd, [gu.to(DEV), gv.to(DEV)])
-    P.close(f"{name}: u", u, u64, extra=_kink(u32, u64))
-    P.close(f"{name}: v", v, v64, extra=_kink(v32, v64))
-    P.close(f"{name}: gx (decompose)", gxd, gxd64, extra=_kink(gxd32, gxd64))
+    close("u", u, u64, u32)
+    close("v", v, v64, v32)
+    close("gx (decompose)", gxd, gxd64, gxd32)
     return mf
 
 
@@ -123,6 +130,52 @@ def test_standalone_bf16_storage(solver, M, N, R):
     xb = x.to(DEV).to(torch.bfloat16)
     xf = xb.float().requires_grad_(True)
     gy = (torch.rand(64, M, N, device=DEV) - 0.5).to(torch.bfloat16)
+    with Launches():
+        yf = mf(xf)
+        (gxf,) = torch.autograd.grad(yf, xf, gy.float())
+        xb.requires_grad_(True)
+        yb = mf(xb)
+        (gxb,) = torch.autograd.grad(yb, xb, gy)
+    assert yb.dtype == torch.bfloat16 and gxb.dtype == torch.bfloat16
+    P.close("y (bf16 storage)", yb, yf, rel=2 * 2.0 ** -8, why="bf16 rounding of the stored output")
+    P.close("gx (bf16 storage)", gxb, gxf, rel=2 * 2.0 ** -8, why="bf16 rounding of the stored gradient")
+
+
+TABLE_SOLVERS = ("mu", "hals", "cd", "smu")
+TABLE_SEED = 63   # of seeds 0..70 the one with the best-conditioned inputs: on the CPU every guard below is under a third of its bound
+
+
+def _table_inputs(solver, R):
+    """3 matrices of 5 x 40 (a partial workgroup; the first row of the shape table with padding in both extents), T = 3, G = 2"""
+    torch.manual_seed(TABLE_SEED + 10 * TABLE_SOLVERS.index(solver) + R)
+    x = torch.randn(3, 5, 40) if solver == "smu" else torch.rand(3, 5, 40)
+    return x, torch.rand(5, R), torch.rand(40, R), torch.rand(3, 5, 40) - 0.5
+
+
+@pytest.mark.parametrize("R", [1, 2, 3, 4])
+@pytest.mark.parametrize("solver", TABLE_SOLVERS)
+def test_launcher_table_fp32(solver, R):
+    """every (solver unit, rank) of the launcher table of csrc/nmf.hip, both directions, fp32 storage: a swapped entry is another
+    rank, solver or direction, i.e. other values.  The conditioning guard of every comparison stays below the bound it is
+    added to, so it cannot hide that."""
+    x, u0, v0, gy = _table_inputs(solver, R)
+    assert Fn.nmf_supported(5, 40, R, 3, 2)
+    guards = []
+    _check_standalone(f"{solver} R{R}", x, u0, v0, 3, 2, solver, gy, guards=guards)
+    assert len(guards) == 5
+    for what, kink, base in guards:
+        assert kink <= base, (solver, R, what, kink, base)
+
+
+@pytest.mark.parametrize("R", [1, 2, 3, 4])
+@pytest.mark.parametrize("solver", TABLE_SOLVERS)
+def test_launcher_table_bf16(solver, R):
+    """the bf16 half of the table: against the fp32 native result on the same rounded inputs, in units of 2^-8"""
+    x, u0, v0, gy = _table_inputs(solver, R)
+    mf = _mf(5, 40, R, 3, 2, solver, u0, v0)
+    xb = x.to(DEV).to(torch.bfloat16)
+    xf = xb.float().requires_grad_(True)
+    gy = gy.to(DEV).to(torch.bfloat16)
     with Launches():
         yf = mf(xf)
         (gxf,) = torch.autograd.grad(yf, xf, gy.float())

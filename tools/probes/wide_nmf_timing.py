@@ -51,8 +51,8 @@ res["fwd_bwd_per_call_gpu_host_ms"] = per_call(lambda: torch.autograd.grad(nmf(t
 # backward alone through the raw entry points (no autograd graph), workspace reused
 u0, v0 = nmf.init.u0.contiguous(), nmf.init.v0.contiguous()
 x = td.detach().contiguous()
-res["raw_fwd_ms"] = batch(lambda: Fn._gnmf_fwd_raw(x, u0, v0, 5, "mu", 1e-16))
-res["raw_bwd_ms"] = batch(lambda: Fn._gnmf_bwd_raw(x, u0, v0, gm, None, None, 5, 5, "mu", 1e-16))
+res["raw_fwd_ms"] = batch(lambda: Fn._nmf_fwd("gnmf", x, u0, v0, 5, "mu", 1e-16))
+res["raw_bwd_ms"] = batch(lambda: Fn._nmf_bwd("gnmf", x, u0, v0, gm, None, None, 5, 5, "mu", 1e-16))
 # with the allocator under pressure (many live blocks): does an allocation in the timed lambda sync?
 junk = [torch.empty(64 * 1024 * 1024, device=dev) for _ in range(40)]
 res["fwd_bwd_batch_ms_with_10GB_live"] = batch(lambda: torch.autograd.grad(nmf(td), td, gm))

@@ -14,9 +14,10 @@ from .layers import MLP, LayerNorm, Linear, PosEmbed, PositionalEmbedding
 from .convs import Conv2d, Conv3d, ConvTranspose2d, ConvTranspose3d
 from .instance_norm import InstanceNorm1d, InstanceNorm2d, InstanceNorm3d, convert_instance_norm, instance_norm
 from .blocks import FactMixer, FactorizerBlock, FactorizerStage
-from .losses import DeepSupervisionLoss, DiceCELoss, deep_supervision_loss, dice_bce_loss, dice_ce_loss
+from .losses import (DeepSupervisionLoss, DiceCELoss, deep_supervision_loss, dice_bce_loss, dice_ce_loss,
+                     dice_ce_softmax_loss, dice_ce_softmax_loss_composed)
 from .metrics import (DiceMetric, HausdorffDistanceMetric, dice_metric, discretize, hausdorff_distance, mask_edges,
-                      segmentation_counts)
+                      multiclass_counts, one_hot_mask, segmentation_counts)
 from .augment import (AugmentParams, BatchAugment, RandCropAugment, affine_resample, augment_batch, crop_augment_batch,
                       draw_augment_params, draw_crop_origins, gaussian_noise_field, gaussian_smooth)
 from .volume import (BRATS_CLASSES, BRATS_LABEL_VALUES, PreparedVolume, foreground_bbox, normalize_intensity, prepare_volume,

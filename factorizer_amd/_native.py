@@ -346,6 +346,11 @@ _SIGS.update({
     "fz_dice_bce_ds_grad": ([_vp, _vp, _vp, _vp, _i] + [_i] * 6 + [_i, _f, _f, _vp, _vp], _i),
     "fz_dice_ce_ds_sums": ([_vp, _vp, _vp, _i, _i] + [_i] * 6 + [_i, _vp], _i),
     "fz_dice_ce_ds_grad": ([_vp, _vp, _vp, _vp, _i, _i] + [_i] * 6 + [_i, _f, _f, _vp, _vp], _i),
+    "fz_dice_sce_sums": ([_vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp], _i),
+    "fz_dice_sce_finish": ([_vp, _i, _i, _i64, _i, _f, _vp, _vp, _vp], _i),
+    "fz_dice_sce_grad": ([_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _i, _f, _f, _vp, _vp], _i),
+    "fz_dice_sce_ds_sums": ([_vp, _vp, _vp, _i, _i] + [_i] * 6 + [_i, _i, _vp], _i),
+    "fz_dice_sce_ds_grad": ([_vp, _vp, _vp, _vp, _i, _i] + [_i] * 6 + [_i, _i, _i, _f, _f, _vp, _vp], _i),
     "fz_rowsum_chunks": ([_i64], _i),
     "fz_rowsum": ([_vp, _vp, _vp, _i, _i, _i64, _i, _vp], _i),
     "fz_ln_fwd": ([_vp] * 5 + [_i, _i, _i64, _f, _i, _vp], _i),
@@ -362,6 +367,8 @@ _SIGS.update({
     "fz_edge_min_dist2_splits": ([_i64, _i64], _i),
     "fz_edge_min_dist2_workspace_bytes": ([_i64, _i64], _i64),
     "fz_edge_min_dist2": ([_vp, _i64, _vp, _i64, _f, _f, _f, _vp, _vp, _vp], _i),
+    "fz_seg_argmax_workspace_bytes": ([_i, _i, _i64], _i64),
+    "fz_seg_argmax": ([_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp], _i),
     "fz_aug_record_floats": ([], _i),
     "fz_aug_resample": ([_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp], _i),
     "fz_aug_smooth": ([_vp, _vp, _i, _i, _vp, _vp] + [_i] * 6 + [_vp], _i),
@@ -384,6 +391,7 @@ _SIGS.update({
     "fz_inorm_bwd": ([_vp] * 7 + [_i64, _i, _i64, _i, _vp, _vp], _i),
 })
 SEG_F32, SEG_BF16, SEG_U8 = 0, 1, 2   # include/factorizer_hip.h: FZ_SEG_* element kinds of fz_seg_counts
+LABEL_U8, LABEL_I64, LABEL_F32 = 0, 1, 2   # FZ_LABEL_*: element kinds of a class-index label map
 VOL_F32, VOL_BF16, VOL_U8, VOL_I16 = 0, 1, 2, 3   # include/factorizer_hip.h: FZ_VOL_* element kinds
 VOL_IMAGE_IN, VOL_IMAGE_OUT, VOL_LABEL_IN, VOL_LOGITS = 0, 1, 2, 3   # FZ_VOL_ROLE_*
 RESPACE_BILINEAR, RESPACE_NEAREST = 0, 1   # FZ_RESPACE_*

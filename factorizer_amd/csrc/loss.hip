@@ -17,6 +17,7 @@
 // not depend on the reader, so fz_dice_ce_finish and the host finish serve both.  No atomics: one partial per
 // (plane | batch item, chunk), combined in a fixed order.
 #include "fz_common.h"
+#include "seg_labels.h"
 
 namespace fz {
 
@@ -283,6 +284,41 @@ __global__ __launch_bounds__(256) void dice_ce_grad(const float* __restrict__ z,
   }
 }
 
+// The finish of the class-index form (dice_sce_* at the end of this section), as dice_ce_finish_kernel below: the Dice mean runs over the channels c >= c0 (B·(C − c0) planes), the planes
+// below c0 get the inert coefficients {0, 1}
+__global__ __launch_bounds__(256) void dice_sce_finish_kernel(const float* __restrict__ part, int nchunk, int B, int C, int c0,
+                                                              float inv_bv, float smooth, float* __restrict__ loss,
+                                                              float* __restrict__ coef) {
+  __shared__ float cols[8 * 49];   // (B <= 8) x (3C + 1 <= 49) column totals
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ncol = 3 * C + 1;
+  for (int col = wave; col < B * ncol; col += 4) {
+    const int b = col / ncol, k = col % ncol;
+    float t = 0.f;
+    for (int ch = lane; ch < nchunk; ch += 64) t += part[((int64_t)b * nchunk + ch) * ncol + k];
+    t = wave_sum(t);
+    if (lane == 0) cols[col] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float dice = 0.f, ce = 0.f;
+    for (int b = 0; b < B; ++b) {
+      for (int c = 0; c < C; ++c) {
+        float num = 0.f, den = 1.f;
+        if (c >= c0) {
+          num = 2.0f * cols[b * ncol + 3 * c] + smooth;
+          den = cols[b * ncol + 3 * c + 1] + cols[b * ncol + 3 * c + 2] + smooth;
+          dice += 1.0f - num / den;
+        }
+        coef[(b * C + c) * 2] = num;
+        coef[(b * C + c) * 2 + 1] = den;
+      }
+      ce += cols[b * ncol + 3 * C];
+    }
+    loss[0] = dice / (float)(B * (C - c0)) + ce * inv_bv;
+  }
+}
+
 // One workgroup turns the partial sums into the loss and the Dice coefficients of the gradient pass: replaces a dozen
 // launch-bound framework kernels (sum over chunks, 2·inter + smooth, den + smooth, 1 - num/den, means) between the two
 // passes.  Chunks are added in a fixed order: lane-strided partial sums, then the wave butterfly of fz_common.h.
@@ -312,6 +348,186 @@ __global__ __launch_bounds__(256) void dice_ce_finish_kernel(const float* __rest
       ce += cols[b * ncol + 3 * C];
     }
     loss[0] = dice / (float)(B * C) + ce * inv_bv;
+  }
+}
+
+// ---- the class-index form: DiceCELoss(softmax=True, to_onehot_y=True, include_background, squared_pred)
+// p = softmax_c(z), t_c = [y == c] from a label map (B, 1, *S) read in its own element type (seg_labels.h) and never
+// stored.  Label readers, as the target readers above: classes(yp, at, C, k) gives the classes of the 4 voxels at `at`.
+template <typename YT>
+struct DenseLabels {
+  using elem = YT;
+  using pos = int64_t;
+  __device__ __forceinline__ int64_t plane(int64_t V) const { return V; }
+  __device__ __forceinline__ pos locate(int64_t v) const { return v; }
+  __device__ __forceinline__ void classes(const YT* yp, pos at, int C, int (&k)[4]) const { label_classes4(yp + at, C, k); }
+};
+
+template <typename YT>
+struct LevelLabels {
+  using elem = YT;
+  struct pos { int64_t off[4]; };
+  DsGeom g;
+  __device__ __forceinline__ int64_t plane(int64_t) const { return g.plane; }
+  __device__ __forceinline__ pos locate(int64_t v) const {
+    pos at;
+    ds_offsets((uint32_t)v, g, at.off);
+    return at;
+  }
+  __device__ __forceinline__ void classes(const YT* yp, const pos& at, int C, int (&k)[4]) const {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) k[e] = label_class(yp[at.off[e]], C);
+  }
+};
+
+// The kernels are compiled for CP = 2 / 3 / 4 / 8 / 16 channel slots; C <= CP is a run-time, workgroup-uniform count.  A slot
+// c >= C loads channel C − 1 again (a valid address, a cache hit) and takes the logit −inf, whose exponential, probability
+// and every sum term are 0: no branch separates the loads of one trip from the arithmetic of another.  Such a slot is never
+// stored.
+template <int CP>
+__device__ __forceinline__ void load_logits(const float* zp, int64_t V, int64_t v, int C, float (&zs)[CP][4]) {
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    load4(zp + (c < C ? c : C - 1) * V + v, zs[c]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) zs[c][e] = c < C ? zs[c][e] : -__builtin_huge_valf();
+  }
+}
+
+// In place: zs[c][e] <- e^{z_c − mx}, mx = max_c z_c; returns their sum.
+template <int CP>
+__device__ __forceinline__ float softmax_exps(float (&zs)[CP][4], int e, float mx) {
+  float se = 0.f;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    zs[c][e] = __expf(zs[c][e] - mx);
+    se += zs[c][e];
+  }
+  return se;
+}
+template <int CP>
+__device__ __forceinline__ float logit_max(const float (&zs)[CP][4], int e) {
+  float mx = zs[0][e];
+#pragma unroll
+  for (int c = 1; c < CP; ++c) mx = fmaxf(mx, zs[c][e]);
+  return mx;
+}
+
+// The workgroup's sums in the fixed order of reduce_store: the 3·C channel sums s[0 .. 3C) to out[0 .. 3C), s[3·CP] to out[3C]
+template <int CP>
+__device__ __forceinline__ void reduce_store_channels(const float (&s)[3 * CP + 1], int C, float* __restrict__ out) {
+  constexpr int N = 3 * CP + 1;
+  __shared__ float red[4][N];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    if (i < 3 * C || i == N - 1) {
+      const float r = wave_sum(s[i]);
+      if (lane == 0) red[wave][i] = r;
+    }
+  __syncthreads();
+  const int i = threadIdx.x;
+  if (i < 3 * C || i == N - 1) out[i < 3 * C ? i : 3 * C] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+}
+
+// part (B, nchunk, 3C + 1): per channel {Σ p t, Σ p² (sq) or Σ p, Σ t}, then Σ CE with CE = log Σ_c e^{z_c − mx} − (z_y − mx),
+// which a common shift of the logits leaves as it is; 0 for a label that names no class
+template <int CP, typename RD>
+__global__ __launch_bounds__(256) void dice_sce_sums(const float* __restrict__ z, const typename RD::elem* __restrict__ y,
+                                                     float* __restrict__ part, int64_t V, int nchunk, int C, int sq, RD rd) {
+  const int b = blockIdx.x, chunk = blockIdx.y;
+  int64_t v0, v1;
+  chunk_bounds(V, nchunk, chunk, v0, v1);
+  const float* zp = z + (int64_t)b * C * V;
+  const typename RD::elem* yp = y + (int64_t)b * rd.plane(V);
+  constexpr int SUMS_TRIPS = CP <= 8 ? 2 : 1;
+  float s[3 * CP + 1];
+#pragma unroll
+  for (int i = 0; i < 3 * CP + 1; ++i) s[i] = 0.f;
+  // two trips at a time where the registers allow it: the pass is one wave per SIMD at the chunk counts of
+  // fz_dice_bce_chunks, so the loads of the second trip in flight during the first one's exponentials are what hides the
+  // memory latency
+#pragma unroll SUMS_TRIPS
+  for (int64_t v = v0 + threadIdx.x * 4; v < v1; v += 1024) {
+    float zs[CP][4];
+    load_logits<CP>(zp, V, v, C, zs);
+    int k[4];
+    rd.classes(yp, rd.locate(v), C, k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float mx = logit_max<CP>(zs, e);
+      float dk = mx;   // z_y
+#pragma unroll
+      for (int c = 0; c < CP; ++c) dk = k[e] == c ? zs[c][e] : dk;
+      dk -= mx;        // z_y − mx
+      const float se = softmax_exps<CP>(zs, e, mx);
+      const float inv = 1.0f / se;
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        const float p = zs[c][e] * inv;
+        const bool hit = k[e] == c;
+        s[3 * c + 0] += hit ? p : 0.f;
+        s[3 * c + 1] += sq ? p * p : p;
+        s[3 * c + 2] += hit ? 1.f : 0.f;
+      }
+      s[3 * CP] += k[e] >= 0 ? __logf(se) - dk : 0.f;
+    }
+  }
+  reduce_store_channels<CP>(s, C, part + ((int64_t)b * nchunk + chunk) * (3 * C + 1));
+}
+
+// coef (B·C, 2) = {num, den};  gz_k = g·[ p_k (a_k − Σ_c a_c p_c) + cb (p_k − t_k) ]  (cb = 0 at a label that names no class),
+// a_c = t_c·A_c + (sq ? p_c : 1)·Q_c with A_c = −2 cd/den_c, Q_c = (sq ? 2 : 1)·cd·num_c/den_c² for c >= c0, else both 0.
+// One batch item per blockIdx.y, so the 2·C plane scalars are workgroup-uniform; the grid-stride loop over the item's V
+// starts past 4096 · 1024 voxels.
+template <int CP, typename RD>
+__global__ __launch_bounds__(256) void dice_sce_grad(const float* __restrict__ z, const typename RD::elem* __restrict__ y,
+                                                     const float* __restrict__ coef, float* __restrict__ gz, int64_t V, int C,
+                                                     int sq, int c0, float cd, float cb, const float* __restrict__ gscale,
+                                                     RD rd) {
+  const int b = blockIdx.y;
+  const float g = gscale ? gscale[0] : 1.0f;
+  float A[CP], Q[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    A[c] = 0.f, Q[c] = 0.f;
+    if (c < C && c >= c0) {
+      const float num = coef[(b * C + c) * 2], den = coef[(b * C + c) * 2 + 1];
+      A[c] = -2.0f * cd / den;
+      Q[c] = (sq ? 2.0f : 1.0f) * cd * num / (den * den);
+    }
+  }
+  const float* zp = z + (int64_t)b * C * V;
+  float* gp = gz + (int64_t)b * C * V;
+  const typename RD::elem* yp = y + (int64_t)b * rd.plane(V);
+  for (int64_t v = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; v < V; v += (int64_t)gridDim.x * 1024) {
+    float zs[CP][4];
+    load_logits<CP>(zp, V, v, C, zs);
+    int k[4];
+    rd.classes(yp, rd.locate(v), C, k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float inv = 1.0f / softmax_exps<CP>(zs, e, logit_max<CP>(zs, e));
+      const float cbv = k[e] >= 0 ? cb : 0.f;   // a label that names no class has no CE term
+      float dot = 0.f;                          // Σ_c a_c p_c
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        const float p = zs[c][e] * inv;
+        zs[c][e] = p;
+        const float a = (k[e] == c ? A[c] : 0.f) + (sq ? p * Q[c] : Q[c]);
+        dot += a * p;
+      }
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        const float p = zs[c][e];
+        const bool hit = k[e] == c;
+        const float a = (hit ? A[c] : 0.f) + (sq ? p * Q[c] : Q[c]);
+        zs[c][e] = g * (p * (a - dot) + cbv * (p - (hit ? 1.f : 0.f)));
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CP; ++c)
+      if (c < C) *reinterpret_cast<float4*>(gp + c * V + v) = make_float4(zs[c][0], zs[c][1], zs[c][2], zs[c][3]);
   }
 }
 
@@ -390,6 +606,58 @@ static bool launch_ce_grad(RD rd, const float* z, const void* t, const float* co
   return by_channels(C, [&](auto cc) {
     hipLaunchKernelGGL((dice_ce_grad<decltype(cc)::value, RD>), dim3(grad_blocks((int64_t)B * V)), dim3(256), 0,
                        (hipStream_t)stream, z, static_cast<const typename RD::elem*>(t), coef, gz, V, B, cd, cb, gscale, rd);
+  });
+}
+
+// ---- the class-index form: f(IntC<CP>{}) for the channel slots, rd(YT{}) the label reader of the element kind ----
+template <typename F>
+static void by_slots(int C, F f) {
+  if (C == 2) f(IntC<2>{});
+  else if (C == 3) f(IntC<3>{});
+  else if (C <= 4) f(IntC<4>{});
+  else if (C <= 8) f(IntC<8>{});
+  else f(IntC<16>{});
+}
+
+// what every fz_dice_sce_* pass refuses; 0 when the call may launch
+static int sce_check(const char* who, bool null, const void* y, int B, int C, int64_t V, int ykind, int c0) {
+  const char* why = nullptr;
+  int code = FZ_E_ARG;
+  if (null) why = "null pointer";
+  else if (!label_kind_ok(ykind)) why = "label kind must be FZ_LABEL_U8 / _I64 / _F32";
+  else if (c0 != 0 && c0 != 1) why = "c0 must be 0 (include_background) or 1";
+  else if (C < 2 || C > 16) why = "2 <= C <= 16", code = FZ_E_UNSUPPORTED;
+  else if (B < 1 || B > 65535) why = "1 <= B <= 65535", code = FZ_E_SHAPE;
+  else if (V < 4 || (V % 4)) why = "V must be a positive multiple of 4", code = FZ_E_SHAPE;
+  else if ((uintptr_t)y % (uintptr_t)label_esize(ykind)) why = "label map not aligned to its element";
+  if (why) return fail(code, (std::string(who) + ": " + why).c_str());
+  return FZ_OK;
+}
+
+template <typename MK>
+static void launch_sce_sums(MK rd_of, int ykind, const float* z, const void* y, float* part, int B, int C, int64_t V, int sq,
+                            fz_stream_t stream) {
+  const int nchunk = fz_dice_bce_chunks(V);
+  by_label_kind(ykind, [&](auto yt) {
+    auto rd = rd_of(yt);
+    using RD = decltype(rd);
+    by_slots(C, [&](auto cp) {
+      hipLaunchKernelGGL((dice_sce_sums<decltype(cp)::value, RD>), dim3(B, nchunk), dim3(256), 0, (hipStream_t)stream, z,
+                         static_cast<const typename RD::elem*>(y), part, V, nchunk, C, sq, rd);
+    });
+  });
+}
+
+template <typename MK>
+static void launch_sce_grad(MK rd_of, int ykind, const float* z, const void* y, const float* coef, float* gz, int B, int C,
+                            int64_t V, int sq, int c0, float cd, float cb, const float* gscale, fz_stream_t stream) {
+  by_label_kind(ykind, [&](auto yt) {
+    auto rd = rd_of(yt);
+    using RD = decltype(rd);
+    by_slots(C, [&](auto cp) {
+      hipLaunchKernelGGL((dice_sce_grad<decltype(cp)::value, RD>), dim3(grad_blocks(V), B), dim3(256), 0, (hipStream_t)stream,
+                         z, static_cast<const typename RD::elem*>(y), coef, gz, V, C, sq, c0, cd, cb, gscale, rd);
+    });
   });
 }
 
@@ -508,6 +776,66 @@ extern "C" int fz_dice_ce_ds_grad(const float* z, const void* t, const float* co
   bool ok = false;
   by_kind(tkind, g, [&](auto rd) { ok = launch_ce_grad(rd, z, t, coef, gz, B, C, V, cd, cb, gscale, stream); });
   if (!ok) return fail(FZ_E_UNSUPPORTED, "fz_dice_ce_ds_grad: 2 <= C <= 8");
+  FZ_LAUNCH_CHECK();
+  return FZ_OK;
+}
+
+// ---- the class-index form (softmax, label map): dense, finish, one coarse level ----
+extern "C" int fz_dice_sce_sums(const float* z, const void* y, float* part, int B, int C, int64_t V, int ykind, int sq,
+                                fz_stream_t stream) {
+  if (int rc = sce_check("fz_dice_sce_sums", !z || !y || !part, y, B, C, V, ykind, 0)) return rc;
+  if ((uintptr_t)y % (uintptr_t)label_vec_bytes(ykind) || (uintptr_t)z % 16)
+    return fail(FZ_E_ARG, "fz_dice_sce_sums: logits and label map must be aligned to their 16-byte (uint8: 4-byte) loads");
+  launch_sce_sums([](auto yt) { return DenseLabels<decltype(yt)>{}; }, ykind, z, y, part, B, C, V, sq, stream);
+  FZ_LAUNCH_CHECK();
+  return FZ_OK;
+}
+
+extern "C" int fz_dice_sce_finish(const float* part, int B, int C, int64_t V, int c0, float smooth, float* loss, float* coef,
+                                  fz_stream_t stream) {
+  if (!part || !loss || !coef) return fail(FZ_E_ARG, "fz_dice_sce_finish: null pointer");
+  if (c0 != 0 && c0 != 1) return fail(FZ_E_ARG, "fz_dice_sce_finish: c0 must be 0 (include_background) or 1");
+  if (B < 1 || B > 8 || C < 2 || C > 16) return fail(FZ_E_UNSUPPORTED, "fz_dice_sce_finish: 1 <= B <= 8, 2 <= C <= 16");
+  if (V < 4 || (V % 4)) return fail(FZ_E_SHAPE, "fz_dice_sce_finish: V must be a positive multiple of 4");
+  hipLaunchKernelGGL(dice_sce_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, fz_dice_bce_chunks(V), B, C, c0,
+                     1.0f / ((float)B * (float)V), smooth, loss, coef);
+  FZ_LAUNCH_CHECK();
+  return FZ_OK;
+}
+
+extern "C" int fz_dice_sce_grad(const float* z, const void* y, const float* coef, float* gz, int B, int C, int64_t V, int ykind,
+                                int sq, int c0, float cd, float cb, const float* gscale, fz_stream_t stream) {
+  if (int rc = sce_check("fz_dice_sce_grad", !z || !y || !coef || !gz, y, B, C, V, ykind, c0)) return rc;
+  if ((uintptr_t)y % (uintptr_t)label_vec_bytes(ykind) || (uintptr_t)z % 16 || (uintptr_t)gz % 16)
+    return fail(FZ_E_ARG, "fz_dice_sce_grad: logits, gradient and label map must be aligned to their 16-byte (uint8: 4-byte) loads");
+  launch_sce_grad([](auto yt) { return DenseLabels<decltype(yt)>{}; }, ykind, z, y, coef, gz, B, C, V, sq, c0, cd, cb, gscale,
+                  stream);
+  FZ_LAUNCH_CHECK();
+  return FZ_OK;
+}
+
+extern "C" int fz_dice_sce_ds_sums(const float* z, const void* y, float* part, int B, int C, int Td, int Th, int Tw, int Ld,
+                                   int Lh, int Lw, int ykind, int sq, fz_stream_t stream) {
+  DsGeom g;
+  int64_t V;
+  if (int rc = ds_geom("fz_dice_sce_ds_sums", Td, Th, Tw, Ld, Lh, Lw, FZ_SEG_F32, &g, &V)) return rc;
+  if (int rc = sce_check("fz_dice_sce_ds_sums", !z || !y || !part, y, B, C, V, ykind, 0)) return rc;
+  if ((uintptr_t)z % 16) return fail(FZ_E_ARG, "fz_dice_sce_ds_sums: logits must be 16-byte aligned");
+  launch_sce_sums([&](auto yt) { return LevelLabels<decltype(yt)>{g}; }, ykind, z, y, part, B, C, V, sq, stream);
+  FZ_LAUNCH_CHECK();
+  return FZ_OK;
+}
+
+extern "C" int fz_dice_sce_ds_grad(const float* z, const void* y, const float* coef, float* gz, int B, int C, int Td, int Th,
+                                   int Tw, int Ld, int Lh, int Lw, int ykind, int sq, int c0, float cd, float cb,
+                                   const float* gscale, fz_stream_t stream) {
+  DsGeom g;
+  int64_t V;
+  if (int rc = ds_geom("fz_dice_sce_ds_grad", Td, Th, Tw, Ld, Lh, Lw, FZ_SEG_F32, &g, &V)) return rc;
+  if (int rc = sce_check("fz_dice_sce_ds_grad", !z || !y || !coef || !gz, y, B, C, V, ykind, c0)) return rc;
+  if ((uintptr_t)z % 16 || (uintptr_t)gz % 16) return fail(FZ_E_ARG, "fz_dice_sce_ds_grad: logits and gradient must be 16-byte aligned");
+  launch_sce_grad([&](auto yt) { return LevelLabels<decltype(yt)>{g}; }, ykind, z, y, coef, gz, B, C, V, sq, c0, cd, cb, gscale,
+                  stream);
   FZ_LAUNCH_CHECK();
   return FZ_OK;
 }

@@ -18,7 +18,12 @@
 //                  target and 4 queries); long target lists are split over blockIdx.y and the partial minima combined in
 //                  split order.  fp32: with unit spacing every difference, square and sum is an integer < 2^24 while no
 //                  axis exceeds 2048 (3 · 2047² = 12 570 627), so the result is exact whatever the order.
+// and for mutually exclusive classes (AsDiscrete(argmax=True, to_onehot=C) and the multi-class DiceMetric):
+//   seg_argmax     one streaming pass over the C logit planes of a batch item (or an already discrete label map) and,
+//                  optionally, a class-index label map: the uint8 class map, the uint8 one-hot mask and the three integer
+//                  counts of every class, chunked, reduced and finished as seg_counts does.
 #include "fz_common.h"
+#include "seg_labels.h"
 
 namespace fz {
 
@@ -140,6 +145,130 @@ __global__ __launch_bounds__(256) void seg_counts_finish_kernel(const uint32_t* 
     __syncthreads();
   }
   if (t < 3) counts[plane * 3 + t] = (int64_t)red[t][0];
+}
+
+// ---- seg_argmax ---------------------------------------------------------------------------------------------------------
+// The classes of NV consecutive voxels of one batch item.  Logits: argmax over the C planes, the running best starting at
+// -inf with class 0 and replaced only by a strictly greater value — ties go to the lowest index, a NaN never wins, an all-NaN
+// (or all -inf) voxel is class 0; bf16 values are compared as stored (their conversion to fp32 is exact).  A uint8 input is a
+// label map already: the class is the stored value (one >= C equals no channel index below).
+template <int NV, typename PT>
+__device__ __forceinline__ void pred_classes(const PT* pp, int64_t V, int64_t v, int C, int CP, int (&pc)[NV]) {
+  float best[NV];
+#pragma unroll
+  for (int e = 0; e < NV; ++e) best[e] = -__builtin_huge_valf(), pc[e] = 0;
+#pragma unroll 16
+  for (int c = 0; c < CP; ++c)
+    if (c < C) {
+      float x[NV];
+      aload<NV>(pp + c * V + v, x);
+#pragma unroll
+      for (int e = 0; e < NV; ++e)
+        if (x[e] > best[e]) best[e] = x[e], pc[e] = c;
+    }
+}
+template <int NV>
+__device__ __forceinline__ void pred_classes(const uint8_t* pp, int64_t, int64_t v, int, int, int (&pc)[NV]) {
+  if constexpr (NV == 4) {
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(pp + v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pc[e] = (int)((w >> (8 * e)) & 0xffu);
+  } else {
+    pc[0] = pp[v];
+  }
+}
+
+// NV voxels of every lane of the wave (`on`: this lane has some): classes, the optional outputs, the ballots of the counts
+template <int NV, int CP, typename PT, typename LT>
+__device__ __forceinline__ void argmax_step(bool on, const PT* pp, const LT* lp, uint8_t* mp, uint8_t* op, int64_t V, int64_t v,
+                                            int C, bool count, uint32_t (&n)[CP][3]) {
+  int pc[NV], yc[NV];
+#pragma unroll
+  for (int e = 0; e < NV; ++e) pc[e] = -1, yc[e] = -1;
+  if (on) {
+    pred_classes<NV>(pp, V, v, C, CP, pc);
+    if (lp) {
+      if constexpr (NV == 4) label_classes4(lp + v, C, yc);
+      else yc[0] = label_class(lp[v], C);
+    }
+    if (mp) {
+      if constexpr (NV == 4)
+        *reinterpret_cast<uint32_t*>(mp + v) = (uint32_t)pc[0] | ((uint32_t)pc[1] << 8) | ((uint32_t)pc[2] << 16) | ((uint32_t)pc[3] << 24);
+      else mp[v] = (uint8_t)pc[0];
+    }
+    if (op) {
+#pragma unroll
+      for (int c = 0; c < CP; ++c)
+        if (c < C) {
+          if constexpr (NV == 4)
+            *reinterpret_cast<uint32_t*>(op + c * V + v) = (uint32_t)(pc[0] == c) | ((uint32_t)(pc[1] == c) << 8) |
+                                                           ((uint32_t)(pc[2] == c) << 16) | ((uint32_t)(pc[3] == c) << 24);
+          else op[c * V + v] = pc[0] == c ? 1 : 0;
+        }
+    }
+  }
+  if (count) {
+#pragma unroll
+    for (int c = 0; c < CP; ++c)
+      if (c < C) {
+#pragma unroll
+        for (int e = 0; e < NV; ++e) {
+          const unsigned long long bp = __ballot(pc[e] == c), by = __ballot(yc[e] == c);
+          n[c][0] += __popcll(bp & by);
+          n[c][1] += __popcll(bp);
+          n[c][2] += __popcll(by);
+        }
+      }
+  }
+}
+
+// grid (nchunk, B); pred (B, C, V) logits or (B, 1, V) uint8 classes; part (B·C, nchunk, 3) uint32, the layout that
+// seg_counts_finish_kernel sums.  CP = 4 / 8 / 16 channel slots, C <= CP at run time.  VEC: V % 4 == 0 and every base pointer
+// is 16-byte aligned: groups of 4 voxels per lane, then (as in seg_counts_kernel) the rest of the chunk one voxel per lane.
+template <typename PT, typename LT, int CP, bool VEC>
+__global__ __launch_bounds__(256) void seg_argmax_kernel(const PT* __restrict__ pred, const LT* __restrict__ label,
+                                                         uint8_t* __restrict__ map, uint8_t* __restrict__ onehot,
+                                                         uint32_t* __restrict__ part, int64_t V, int64_t per, int nchunk, int C) {
+  __shared__ uint32_t red[4][CP * 3];
+  constexpr bool LOGITS = !std::is_same<PT, uint8_t>::value;
+  const int chunk = blockIdx.x, b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t v0 = (int64_t)chunk * per, v1 = min(V, v0 + per);
+  const PT* pp = pred + (int64_t)b * (LOGITS ? C : 1) * V;
+  const LT* lp = label ? label + (int64_t)b * V : nullptr;
+  uint8_t* mp = map ? map + (int64_t)b * V : nullptr;
+  uint8_t* op = onehot ? onehot + (int64_t)b * C * V : nullptr;
+  const bool count = part != nullptr;
+  uint32_t n[CP][3];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) n[c][0] = n[c][1] = n[c][2] = 0;
+  int64_t tail0 = v0;
+  if constexpr (VEC) {
+    const int64_t g1 = v0 + ((v1 - v0) & ~(int64_t)3);   // whole groups of 4 (v0 is a multiple of 4)
+    for (int64_t base = v0 + wave * 256; base < g1; base += 1024) {
+      const int64_t v = base + lane * 4;
+      argmax_step<4, CP>(v < g1, pp, lp, mp, op, V, v, C, count, n);
+    }
+    tail0 = g1;
+  }
+  for (int64_t base = tail0 + wave * 64; base < v1; base += 256) {
+    const int64_t v = base + lane;
+    argmax_step<1, CP>(v < v1, pp, lp, mp, op, V, v, C, count, n);
+  }
+  if (count) {
+    if (lane == 0) {
+#pragma unroll
+      for (int c = 0; c < CP; ++c)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) red[wave][c * 3 + e] = n[c][e];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * C) {
+      const int c = threadIdx.x / 3, e = threadIdx.x % 3;
+      part[(((int64_t)b * C + c) * nchunk + chunk) * 3 + e] =
+          (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    }
+  }
 }
 
 // ---- mask_edges ---------------------------------------------------------------------------------------------------------
@@ -269,6 +398,25 @@ static void seg_counts_label(int label_kind, bool vec, const void* pred, const v
   else seg_counts_launch<PT, PGE, uint8_t>(vec, pred, label, mask, part, bound, planes, V, s);
 }
 
+template <typename PT, typename LT>
+static void seg_argmax_launch(bool vec, const void* pred, const void* label, uint8_t* map, uint8_t* onehot, uint32_t* part,
+                              int B, int C, int64_t V, hipStream_t s) {
+  const int64_t per = seg_per(V);
+  const int nchunk = (int)((V + per - 1) / per);
+  const dim3 grid(nchunk, B), block(256);
+  auto go = [&](auto cp, auto vc) {
+    hipLaunchKernelGGL((seg_argmax_kernel<PT, LT, decltype(cp)::value, decltype(vc)::value>), grid, block, 0, s, (const PT*)pred,
+                       (const LT*)label, map, onehot, part, V, per, nchunk, C);
+  };
+  auto slots = [&](auto vc) {
+    if (C <= 4) go(std::integral_constant<int, 4>{}, vc);
+    else if (C <= 8) go(std::integral_constant<int, 8>{}, vc);
+    else go(std::integral_constant<int, 16>{}, vc);
+  };
+  if (vec) slots(std::true_type{});
+  else slots(std::false_type{});
+}
+
 // target splits of a (nq, nt) problem: enough workgroups for the chip (about 1024) when the query blocks alone are few, never
 // more than the target tiles or 64; `per` targets per split, a multiple of the tile
 static int md_splits(int64_t nq, int64_t nt, int64_t* per_out) {
@@ -317,6 +465,41 @@ extern "C" int fz_seg_counts(const void* pred, int pred_kind, const void* label,
   FZ_LAUNCH_CHECK();
   if (counts) {
     hipLaunchKernelGGL(seg_counts_finish_kernel, dim3(planes), dim3(256), 0, s, part, fz_seg_counts_chunks(V), counts);
+    FZ_LAUNCH_CHECK();
+  }
+  return FZ_OK;
+}
+
+extern "C" int64_t fz_seg_argmax_workspace_bytes(int B, int C, int64_t V) {
+  if (B < 1 || C < 1 || V < 1) return -1;
+  return (int64_t)B * C * fz_seg_counts_chunks(V) * 3 * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int fz_seg_argmax(const void* pred, int pred_kind, const void* label, int label_kind, uint8_t* map, uint8_t* onehot,
+                             void* workspace, int64_t* counts, int B, int C, int64_t V, fz_stream_t stream) {
+  if (!pred) return fail(FZ_E_ARG, "fz_seg_argmax: null pred");
+  if (!seg_kind_ok(pred_kind)) return fail(FZ_E_ARG, "fz_seg_argmax: pred kind must be FZ_SEG_F32 / _BF16 / _U8");
+  if (label && !label_kind_ok(label_kind)) return fail(FZ_E_ARG, "fz_seg_argmax: label kind must be FZ_LABEL_U8 / _I64 / _F32");
+  if (!map && !onehot && !counts) return fail(FZ_E_ARG, "fz_seg_argmax: no output requested");
+  if (counts && !workspace) return fail(FZ_E_ARG, "fz_seg_argmax: counts need the workspace");
+  if (C < 2 || C > 16) return fail(FZ_E_UNSUPPORTED, "fz_seg_argmax: 2 <= C <= 16");
+  if (B < 1 || B > 65535 || V < 1) return fail(FZ_E_SHAPE, "fz_seg_argmax: 1 <= B <= 65535, V >= 1");
+  if (!seg_aligned(pred, seg_esize(pred_kind)) || (label && !seg_aligned(label, label_esize(label_kind))) ||
+      !seg_aligned(counts, 8) || !seg_aligned(workspace, 4))
+    return fail(FZ_E_ARG, "fz_seg_argmax: pointer not aligned to its element");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = V % 4 == 0 && seg_aligned(pred, 16) && seg_aligned(label, 16) && seg_aligned(map, 16) && seg_aligned(onehot, 16);
+  uint32_t* part = counts ? (uint32_t*)workspace : nullptr;
+  const int lk = label ? label_kind : FZ_LABEL_U8;
+  by_label_kind(lk, [&](auto yt) {
+    using LT = decltype(yt);
+    if (pred_kind == FZ_SEG_F32) seg_argmax_launch<float, LT>(vec, pred, label, map, onehot, part, B, C, V, s);
+    else if (pred_kind == FZ_SEG_BF16) seg_argmax_launch<bf16, LT>(vec, pred, label, map, onehot, part, B, C, V, s);
+    else seg_argmax_launch<uint8_t, LT>(vec, pred, label, map, onehot, part, B, C, V, s);
+  });
+  FZ_LAUNCH_CHECK();
+  if (counts) {
+    hipLaunchKernelGGL(seg_counts_finish_kernel, dim3(B * C), dim3(256), 0, s, part, fz_seg_counts_chunks(V), counts);
     FZ_LAUNCH_CHECK();
   }
   return FZ_OK;

@@ -796,6 +796,37 @@ def seg_counts(pred, label, bound, want_mask=False, want_counts=True):
     return counts, mask
 
 
+LABEL_KIND = {torch.uint8: N.LABEL_U8, torch.int64: N.LABEL_I64, torch.float32: N.LABEL_F32}
+
+
+def label_kind_ok(t) -> bool:
+    """a class-index label map the kernels read in its own type: uint8 / int64 / fp32, contiguous, 16-byte aligned"""
+    return t.dtype in LABEL_KIND and t.is_contiguous() and t.data_ptr() % 16 == 0
+
+
+def seg_argmax(pred, label, num_classes, want_map=False, want_onehot=False, want_counts=False):
+    """One pass of fz_seg_argmax over `pred` — logits (B, C, *S) of a native float kind, or a uint8 label map (B, 1, *S) of
+    `num_classes` classes — and the optional class-index `label` (B, 1, *S).  Returns (map, onehot, counts): uint8
+    (B, 1, *S), uint8 (B, C, *S), int64 (B, C, 3) = {|P = c ∧ Y = c|, |P = c|, |Y = c|}, each None unless asked for."""
+    B, C = pred.shape[0], int(num_classes)
+    sp = tuple(pred.shape[2:])
+    V = math.prod(sp)
+    lib = N.lib()
+    dev = pred.device
+    cmap = torch.empty((B, 1, *sp), dtype=torch.uint8, device=dev) if want_map else None
+    onehot = torch.empty((B, C, *sp), dtype=torch.uint8, device=dev) if want_onehot else None
+    counts = torch.empty((B, C, 3), dtype=torch.int64, device=dev) if want_counts else None
+    ws = torch.empty(int(lib.fz_seg_argmax_workspace_bytes(B, C, V)) // 4, dtype=torch.int32, device=dev) if want_counts else None
+    nbytes = pred.numel() * pred.element_size() + (label.numel() * label.element_size() if label is not None else 0) + \
+        (B * V if want_map else 0) + (B * C * V if want_onehot else 0)
+    with _dev_guard(pred):
+        rc = _timed("seg_argmax", nbytes, lambda: lib.fz_seg_argmax(
+            pred.data_ptr(), _SEG_KIND[pred.dtype], N.ptr(label), LABEL_KIND[label.dtype] if label is not None else 0,
+            N.ptr(cmap), N.ptr(onehot), N.ptr(ws), N.ptr(counts), B, C, V, N.stream_ptr(pred)), cols=B * V)
+    N.check(rc, "fz_seg_argmax")
+    return cmap, onehot, counts
+
+
 def mask_edges(mask):
     """fz_mask_edges over a one-byte mask (B, C, *S) with 1 to 3 spatial axes: (edges uint8 like mask, counts int64 (B, C))"""
     B, C = mask.shape[:2]

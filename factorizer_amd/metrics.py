@@ -23,6 +23,23 @@ against it:
   the two directions (``torch.max``), so it is NaN whenever either edge set is empty;
 * reductions (``do_metric_reduction``): NaN entries are left out of every mean; a mean over nothing is 0.0.
 
+Mutually exclusive classes (``argmax=True``; the bundle chain ``AsDiscreted(pred, argmax=True, to_onehot=C)`` +
+``AsDiscreted(label, to_onehot=C)`` + ``DiceMetric``), restated the same way:
+
+* argmax over channels with **ties to the lowest index**; the comparison is strict (``z_c > best``, the best starting at
+  −inf with class 0), so a NaN never wins and an all-NaN voxel gives class 0; the decision is taken on the stored values —
+  bf16 logits are compared as stored.  This equals ``AsDiscrete(argmax=True)`` on the CPU for NaN-free input.  The composed
+  branch implements lowest-index explicitly (``where(z == amax, arange, C).amin(1)``), it does not trust ``torch.argmax``;
+* multi-class Dice: per (sample, class) the three exact integer counts ``|P=c ∧ Y=c|``, ``|P=c|`` and ``|Y=c|`` of the
+  predicted and the labelled class maps go through the same `_dice_from_counts` (``include_background``, ``ignore_empty``);
+* labels follow the loss's conventions (factorizer_amd/losses.py): converted as ``.long()`` does, a label outside [0, C)
+  matches no class.
+
+Native (`fz_seg_argmax`: one streaming pass, any V) for fp32 / bf16 device logits with 2 <= C <= 16 and uint8 / int64 / fp32
+label maps; a label map given as the *prediction* (or to `one_hot_mask`) is native as uint8.  fp16 / fp64 logits, C > 16 and
+other label types run composed ops on device and say so once.  A multi-class ``restore_prediction`` and surface Dice are
+not built.
+
 Device tensors run the kernels of csrc/segmetric.hip: one streaming pass for the three integer counts (and the mask), one for
 the edges, and a brute-force nearest-edge search over the two SURFACE lists (DESIGN.md §3.11 says why that beats a
 separable distance transform here).  CPU tensors run composed framework ops; device tensors outside the native gate (fp16 /
@@ -86,10 +103,121 @@ def _decide(x, sigmoid, threshold):
     return (x.float() if x.dtype in (torch.bfloat16, torch.float16) else x) >= b
 
 
-def discretize(x, sigmoid: bool = True, threshold: float = 0.5):
+# ---- mutually exclusive classes: argmax, one-hot, counts -------------------------------------------------------------------
+MAX_CLASSES = 16   # channel slots of fz_seg_argmax
+
+
+def _argmax_only(argmax, sigmoid, threshold):
+    if argmax and (not sigmoid or threshold != 0.5):
+        raise ValueError("argmax=True decides by the largest logit: it takes neither sigmoid=False nor a threshold")
+
+
+def _argmax_composed(x):
+    """int64 (B, *S): argmax over dim 1, ties to the lowest index, a NaN never wins (all NaN: class 0)"""
+    z = x.float() if x.dtype in (torch.bfloat16, torch.float16) else x
+    z = torch.where(torch.isnan(z), torch.full_like(z, -math.inf), z)
+    C = z.shape[1]
+    cls = torch.arange(C, device=z.device).view(1, C, *([1] * (z.dim() - 2)))
+    return torch.where(z == z.amax(1, keepdim=True), cls, C).amin(1)
+
+
+def _one_hot_composed(idx, valid, C):
+    """uint8 (B, C, *S) from int64 classes (B, *S); all-zero rows where not valid"""
+    cls = torch.arange(C, device=idx.device).view(1, C, *([1] * (idx.dim() - 1)))
+    hit = idx.unsqueeze(1) == cls
+    return (hit if valid is None else hit & valid.unsqueeze(1)).to(torch.uint8)
+
+
+def _logits_native(x) -> bool:
+    return x.is_cuda and x.numel() > 0 and x.dtype in (torch.float32, torch.bfloat16) and 2 <= x.shape[1] <= MAX_CLASSES \
+        and x.shape[0] <= 65535
+
+
+def _warn_mc(what, why, *ts):
+    if any(t.is_cuda and t.numel() for t in ts):
+        composed.warn_once(f"metrics:{what}:{why}", f"{what}: {why} is outside the native argmax kernel (fp32 / bf16 logits, "
+                           f"2 <= C <= {MAX_CLASSES}, uint8 / int64 / float32 label maps): composed framework ops")
+
+
+def _mc_why(x):
+    return f"{x.dtype} logits" if x.dtype not in (torch.float32, torch.bfloat16) else f"C = {x.shape[1]}"
+
+
+def _check_mc(pred, labels=None):
+    if pred.dim() < 3 or pred.dim() > 5:
+        raise ValueError("segmentation metrics take (B, C, *S) tensors with 1, 2 or 3 spatial axes")
+    if labels is not None and (labels.dim() != pred.dim() or labels.shape[1] != 1 or labels.shape[0] != pred.shape[0]
+                               or labels.shape[2:] != pred.shape[2:]):
+        raise ValueError(f"prediction {tuple(pred.shape)} needs a label map (B, 1, *S), got {tuple(labels.shape)}")
+
+
+def _discretize_argmax(x, to_onehot):
+    _check_mc(x)
+    if x.shape[1] < 2:
+        raise ValueError(f"argmax=True needs at least two channels, got {tuple(x.shape)}")
+    if _logits_native(x):
+        cmap, onehot, _ = Fn.seg_argmax(x.contiguous(), None, x.shape[1], want_map=not to_onehot, want_onehot=to_onehot)
+        return onehot if to_onehot else cmap
+    _warn_mc("discretize", _mc_why(x), x)
+    idx = _argmax_composed(x)
+    return _one_hot_composed(idx, None, x.shape[1]) if to_onehot else idx.unsqueeze(1).to(torch.uint8)
+
+
+def one_hot_mask(labels, num_classes: int):
+    """``AsDiscrete(to_onehot=num_classes)`` of a class-index label map (B, 1, *S): the uint8 mask (B, C, *S) that
+    `mask_edges` / `hausdorff_distance` take.  A label outside [0, C) gives an all-zero row (the loss's convention)."""
+    _check_mc(labels)
+    C = int(num_classes)
+    if labels.shape[1] != 1 or C < 1:
+        raise ValueError(f"one_hot_mask takes a label map (B, 1, *S) and num_classes >= 1, got {tuple(labels.shape)}, {C}")
+    if labels.is_cuda and labels.numel() and labels.dtype == torch.uint8 and 2 <= C <= MAX_CLASSES and labels.shape[0] <= 65535:
+        return Fn.seg_argmax(labels.contiguous(), None, C, want_onehot=True)[1]
+    _warn_mc("one_hot_mask", f"a {labels.dtype} label map" if labels.dtype != torch.uint8 else f"C = {C}", labels)
+    from .losses import _label_classes
+    return _one_hot_composed(*_label_classes(labels, C), C)
+
+
+def multiclass_counts(pred, labels, num_classes: int | None = None):
+    """int64 (B, C, 3): per (sample, class) |P = c ∧ Y = c|, |P = c| and |Y = c| as exact integers.  ``pred`` holds logits
+    (B, C, *S) — P is their argmax, see the module docstring — or an already discrete label map (B, 1, *S), which needs
+    ``num_classes``; ``labels`` is the class-index label map (B, 1, *S)."""
+    _check_mc(pred, labels)
+    is_map = pred.shape[1] == 1
+    if is_map and num_classes is None:
+        raise ValueError("multiclass_counts: a label map as the prediction needs num_classes")
+    C = int(num_classes) if num_classes is not None else pred.shape[1]
+    if not is_map and C != pred.shape[1]:
+        raise ValueError(f"multiclass_counts: num_classes = {C} against logits {tuple(pred.shape)}")
+    pred_ok = (pred.is_cuda and pred.numel() > 0 and pred.dtype == torch.uint8 and 2 <= C <= MAX_CLASSES
+               and pred.shape[0] <= 65535) if is_map else _logits_native(pred)
+    if pred_ok and labels.is_cuda and labels.dtype in Fn.LABEL_KIND:
+        return Fn.seg_argmax(pred.contiguous(), labels.contiguous(), C, want_counts=True)[2]
+    why = (f"a {pred.dtype} label map" if is_map and pred.dtype != torch.uint8 else
+           _mc_why(pred) if not is_map and not _logits_native(pred) else
+           f"a {labels.dtype} label map" if labels.dtype not in Fn.LABEL_KIND else f"C = {C}")
+    _warn_mc("multiclass_counts", why, pred, labels)
+    from .losses import _label_classes
+    if is_map:
+        p, pv = _label_classes(pred, C)
+    else:
+        p, pv = _argmax_composed(pred), None
+    y, yv = _label_classes(labels, C)
+    P, Y = _one_hot_composed(p, pv, C).bool(), _one_hot_composed(y, yv, C).bool()
+    dims = tuple(range(2, P.dim()))
+    return torch.stack([(P & Y).sum(dims), P.sum(dims), Y.sum(dims)], dim=-1).to(torch.int64)
+
+
+def discretize(x, sigmoid: bool = True, threshold: float = 0.5, argmax: bool = False, to_onehot: bool = False):
     """``Activations(sigmoid)`` + ``AsDiscrete(threshold)``: uint8 mask, 1 iff ``sigmoid(x) >= threshold`` (decided on the
     logit, see the module docstring); with ``sigmoid=False`` ``x`` is a probability or mask and the test is
-    ``x >= threshold``.  A uint8 / bool ``x`` is already discrete: non-zero is foreground."""
+    ``x >= threshold``.  A uint8 / bool ``x`` is already discrete: non-zero is foreground.
+    ``argmax=True``: ``AsDiscrete(argmax=True)`` — the uint8 class map (B, 1, *S), ties to the lowest index — or, with
+    ``to_onehot=True``, ``AsDiscrete(argmax=True, to_onehot=C)``: the uint8 mask (B, C, *S)."""
+    _argmax_only(argmax, sigmoid, threshold)
+    if argmax:
+        return _discretize_argmax(x, to_onehot)
+    if to_onehot:
+        raise ValueError("to_onehot=True belongs to argmax=True (a label map goes through one_hot_mask)")
     _check(x)
     if _native(x):
         return Fn.seg_counts(x.contiguous(), None, _bound(sigmoid, threshold), want_mask=True, want_counts=False)[1]
@@ -129,10 +257,15 @@ def _dice_from_counts(counts, include_background, ignore_empty):
 
 
 def dice_metric(pred, label, *, sigmoid: bool = True, threshold: float = 0.5, include_background: bool = True,
-                ignore_empty: bool = False):
+                ignore_empty: bool = False, argmax: bool = False):
     """MONAI 1.4 ``DiceMetric`` values, float32 (B, C): ``2 |P∧Y| / (|P| + |Y|)`` where |Y| > 0; where the label plane is
     empty NaN (``ignore_empty=True``), else 1.0 if the prediction is empty as well and 0.0 if not.  The quotient is formed
-    from the exact counts in float64 and rounded once.  ``include_background=False`` drops channel 0."""
+    from the exact counts in float64 and rounded once.  ``include_background=False`` drops channel 0.
+    ``argmax=True``: mutually exclusive classes — ``pred`` logits (B, C, *S), ``label`` a class-index map (B, 1, *S), the
+    counts those of `multiclass_counts`."""
+    _argmax_only(argmax, sigmoid, threshold)
+    if argmax:
+        return _dice_from_counts(multiclass_counts(pred, label), include_background, ignore_empty)
     return _dice_from_counts(segmentation_counts(pred, label, sigmoid, threshold), include_background, ignore_empty)
 
 
@@ -200,18 +333,20 @@ class _Cumulative:
 class DiceMetric(_Cumulative):
     """``DiceMetric(include_background, reduction, ignore_empty)`` of the recipe behind the bundle's post-processing
     (``sigmoid`` / ``threshold``: the ``Activationsd`` / ``AsDiscreted`` in front of it; pass ``sigmoid=False`` or masks for
-    already discrete predictions).  ``metric(pred, label)`` returns the (B, C) values and keeps them; ``aggregate()`` reduces
+    already discrete predictions; ``argmax=True``: logits of mutually exclusive classes against a class-index label map,
+    `multiclass_counts`).  ``metric(pred, label)`` returns the (B, C) values and keeps them; ``aggregate()`` reduces
     everything kept since ``reset()``."""
 
     def __init__(self, include_background: bool = True, reduction: str = "mean", ignore_empty: bool = False,
-                 sigmoid: bool = True, threshold: float = 0.5):
+                 sigmoid: bool = True, threshold: float = 0.5, argmax: bool = False):
         super().__init__(reduction)
+        _argmax_only(argmax, sigmoid, threshold)
         self.include_background, self.ignore_empty = include_background, ignore_empty
-        self.sigmoid, self.threshold = sigmoid, threshold
+        self.sigmoid, self.threshold, self.argmax = sigmoid, threshold, argmax
 
     def _compute(self, pred, label):
         return dice_metric(pred, label, sigmoid=self.sigmoid, threshold=self.threshold,
-                           include_background=self.include_background, ignore_empty=self.ignore_empty)
+                           include_background=self.include_background, ignore_empty=self.ignore_empty, argmax=self.argmax)
 
 
 # ---- edges and the Hausdorff distance --------------------------------------------------------------------------------------
@@ -333,13 +468,19 @@ def hausdorff_distance(pred_mask, label_mask, *, percentile=95, spacing=None, di
 class HausdorffDistanceMetric(_Cumulative):
     """``HausdorffDistanceMetric(include_background, percentile, directed, reduction)`` over discrete masks, accumulating as
     `DiceMetric` does; ``spacing`` as in `hausdorff_distance`.  The defaults are MONAI's — ``include_background=False``,
-    ``percentile=None`` — and the bundles pass ``include_background=True, percentile=95`` (train.yaml:279-287)."""
+    ``percentile=None`` — and the bundles pass ``include_background=True, percentile=95`` (train.yaml:279-287).
+    ``argmax=True``: ``pred`` is logits (B, C, *S) and ``label`` a class-index map (B, 1, *S); both become one-hot masks
+    (`discretize(argmax=True, to_onehot=True)`, `one_hot_mask`) in front of the same `hausdorff_distance`."""
 
     def __init__(self, include_background: bool = False, percentile=None, directed: bool = False, reduction: str = "mean",
-                 spacing=None):
+                 spacing=None, argmax: bool = False):
         super().__init__(reduction)
         self.include_background, self.percentile, self.directed, self.spacing = include_background, percentile, directed, spacing
+        self.argmax = argmax
 
     def _compute(self, pred, label):
+        if self.argmax:
+            _check_mc(pred, label)
+            pred, label = discretize(pred, argmax=True, to_onehot=True), one_hot_mask(label, pred.shape[1])
         return hausdorff_distance(pred, label, percentile=self.percentile, spacing=self.spacing, directed=self.directed,
                                   include_background=self.include_background)

@@ -786,6 +786,37 @@ int fz_dice_ce_ds_sums(const float* z, const void* t, float* part, int B, int C,
 int fz_dice_ce_ds_grad(const float* z, const void* t, const float* coef, float* gz, int B, int C, int Td, int Th, int Tw,
                        int Ld, int Lh, int Lw, int tkind, float cd, float cb, const float* gscale, fz_stream_t stream);
 
+/* ---- the class-index form: DiceCELoss(softmax=True, to_onehot_y=True, include_background, squared_pred) of MONAI 1.4 as
+ * restated in factorizer_amd/losses.py.  z (B, C, V) fp32 logits, 2 <= C <= 16, V a positive multiple of
+ * 4; y (B, 1, V) a class-index label map of element kind ykind = FZ_LABEL_U8 / FZ_LABEL_I64 / FZ_LABEL_F32, 16-byte aligned
+ * (4 for uint8), read in its own type: a float label truncates toward zero, a label outside [0, C) (NaN included) matches no
+ * class — its one-hot row is all zero and its CE term is 0, yet it counts in the CE mean's B*V.  With p = softmax_c(z), the
+ * maximum subtracted first, and t_c = [y == c] (never stored):
+ * sums: part (B, fz_dice_bce_chunks(V), 3C+1) = per channel {sum p t, sum p^2 (sq != 0) or sum p, sum t}, then
+ *   sum (logsumexp_c z - z_y).  All C channels are summed; the finish and the gradient leave out those below c0.
+ * finish: loss = mean_{b, c >= c0}(1 - num/den) + sum(CE)/(B V), coef (B*C, 2) = {num = 2 inter + s, den = pred + ground + s}
+ *   ({0, 1} for c < c0), chunks added in a fixed order; B <= 8, c0 = 0 (include_background) or 1.
+ * grad: gz_k = gscale * [ p_k (a_k - sum_c a_c p_c) + cb (p_k - t_k) ],  a_c = cd (-2 t_c/den_c + num_c (sq ? 2 p_c : 1)/den_c^2)
+ *   for c >= c0, else 0;  cd = 1/(B (C - c0)), cb = 1/(B V), taken as 0 at a voxel whose label matches no class.
+ * ds: one coarse deep-supervision level against the full-resolution label map (B, 1, Td, Th, Tw), geometry and index map as
+ *   fz_dice_ce_ds_*; layouts, chunking and summation order are the dense passes'.
+ * FZ_E_ARG: null or misaligned pointer, bad ykind, c0 outside {0, 1}; FZ_E_UNSUPPORTED: C outside 2..16 (finish: B > 8);
+ * FZ_E_SHAPE: V % 4 != 0, a level of 2^31 voxels or more, extents that do not divide. */
+#define FZ_LABEL_U8 0
+#define FZ_LABEL_I64 1
+#define FZ_LABEL_F32 2
+int fz_dice_sce_sums(const float* z, const void* y, float* part, int B, int C, int64_t V, int ykind, int sq,
+                     fz_stream_t stream);
+int fz_dice_sce_finish(const float* part, int B, int C, int64_t V, int c0, float smooth, float* loss, float* coef,
+                       fz_stream_t stream);
+int fz_dice_sce_grad(const float* z, const void* y, const float* coef, float* gz, int B, int C, int64_t V, int ykind, int sq,
+                     int c0, float cd, float cb, const float* gscale, fz_stream_t stream);
+int fz_dice_sce_ds_sums(const float* z, const void* y, float* part, int B, int C, int Td, int Th, int Tw, int Ld, int Lh,
+                        int Lw, int ykind, int sq, fz_stream_t stream);
+int fz_dice_sce_ds_grad(const float* z, const void* y, const float* coef, float* gz, int B, int C, int Td, int Th, int Tw,
+                        int Ld, int Lh, int Lw, int ykind, int sq, int c0, float cd, float cb, const float* gscale,
+                        fz_stream_t stream);
+
 /* ---- sliding-window inference stitching -------------------------------------
  * What MONAI's SlidingWindowInfererAdapt(roi 128^3, sw_batch 2, overlap 0.5, mode "gaussian") does
  * around the network (model_zoo/factorizer_brats23/configs/inference.yaml:96-102, train.yaml:206-212):
@@ -854,6 +885,20 @@ int fz_edge_min_dist2_splits(int64_t nq, int64_t nt);
 int64_t fz_edge_min_dist2_workspace_bytes(int64_t nq, int64_t nt);
 int fz_edge_min_dist2(const float* q, int64_t nq, const float* t, int64_t nt, float w0, float w1, float w2, float* out,
                       void* workspace, fz_stream_t stream);
+/* fz_seg_argmax: the multi-class post-processing AsDiscrete(argmax=True[, to_onehot=C]) and the counts of the multi-class
+ *   DiceMetric in one streaming pass.  pred: logits (B, C, V) of kind FZ_SEG_F32 / FZ_SEG_BF16 — the class
+ *   of a voxel is the argmax over channels, ties to the LOWEST index, the comparison strict on the stored values (z_c > best),
+ *   so a NaN never wins and an all-NaN voxel is class 0 — or, with FZ_SEG_U8, an already discrete label map (B, 1, V) whose
+ *   value is the class (a value >= C matches no class).  label (B, 1, V), optional, of kind FZ_LABEL_*: converted as the
+ *   loss converts it.  Outputs, each optional, at least one required: map (B, 1, V) uint8 class indices; onehot (B, C, V)
+ *   uint8 0 / 1; counts (B, C, 3) int64 = {|P = c and Y = c|, |P = c|, |Y = c|}, exact: uint32 partials (B, C, chunks, 3)
+ *   per workgroup in `workspace` (fz_seg_argmax_workspace_bytes(B, C, V) bytes, required with counts), summed in a fixed
+ *   order by a second launch.  Any V >= 1; 4 voxels per lane when V % 4 == 0 and every pointer is 16-byte aligned, else
+ *   one.  2 <= C <= 16.  FZ_E_ARG: null pred, no output, bad kind, null workspace with counts, a pointer not aligned to
+ *   its element; FZ_E_UNSUPPORTED: C outside 2..16; FZ_E_SHAPE: B < 1, B > 65535 or V < 1. */
+int64_t fz_seg_argmax_workspace_bytes(int B, int C, int64_t V);
+int fz_seg_argmax(const void* pred, int pred_kind, const void* label, int label_kind, uint8_t* map, uint8_t* onehot,
+                  void* workspace, int64_t* counts, int B, int C, int64_t V, fz_stream_t stream);
 
 /* ---- random training augmentations of the recipe, on device (csrc/augment.hip; semantics: factorizer_amd/augment.py) ----
  * `random_transforms` of every bundle (model_zoo/factorizer_brats23/configs/train.yaml): RandAffined, RandGaussianNoised,

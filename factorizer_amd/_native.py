@@ -1,4 +1,8 @@
-"""ctypes binding of libfactorizer_hip.so (C ABI: include/factorizer_hip.h).
+"""ctypes binding of libfactorizer_hip.so, derived from its C ABI in include/factorizer_hip.h.
+
+Argument lists, descriptor layouts and constants are built at import from what _header.py reads in the header: a new entry
+point, field or constant is declared there and nowhere else.  What the header cannot say is stated below, one entry at a time
+(_ARG_EXCEPTIONS, _FIELD_NAMES).
 
 The native library is the product path for device tensors.  There is no silent fallback: if a
 device tensor reaches an op and the library cannot be loaded, `lib()` raises.
@@ -11,16 +15,34 @@ import threading
 
 import torch
 
+from . import _header
+from ._header import NativeError  # noqa: F401  (the package's one error type of the native path)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FZ_LIB_PATH: diagnostics only (A/B of two builds of this library on one box, tools/probes/build_alt.py)
 LIB_PATH = os.environ.get("FZ_LIB_PATH") or os.path.join(_HERE, "libfactorizer_hip.so")
 
-FZ_OK = 0
-FZ_E_UNSUPPORTED = -2
-ABI_VERSION = 7   # include/factorizer_hip.h: FZ_ABI_VERSION this binding's argument lists / descriptor layouts are written against
-SOLVER_ID = {"mu": 0, "hals": 1, "cd": 2, "smu": 3}
-STORE_F32, STORE_BF16 = 0, 1   # include/factorizer_hip.h: FZ_STORE_*
-PRODUCTS_DEFAULT, PRODUCTS_SPLIT_BF16, PRODUCTS_FP32_MFMA = 0, 1, 2   # FZ_PRODUCTS_*: the `products` field of the descriptors
+_H = _header.read()
+
+
+def constants(*names):
+    """the values of the header's `#define FZ_<name>`, in the order asked for"""
+    return tuple(_H.defines["FZ_" + n] for n in names)
+
+
+FZ_OK, FZ_E_UNSUPPORTED = constants("OK", "E_UNSUPPORTED")
+ABI_VERSION, = constants("ABI_VERSION")   # lib() loads only a library that was built from this header
+SOLVER_ID = dict(zip(("mu", "hals", "cd", "smu"), constants("SOLVER_MU", "SOLVER_HALS", "SOLVER_CD", "SOLVER_SMU")))
+STORE_F32, STORE_BF16 = constants("STORE_F32", "STORE_BF16")
+# the `products` field of the descriptors
+PRODUCTS_DEFAULT, PRODUCTS_SPLIT_BF16, PRODUCTS_FP32_MFMA = constants("PRODUCTS_DEFAULT", "PRODUCTS_SPLIT_BF16", "PRODUCTS_FP32_MFMA")
+SEG_F32, SEG_BF16, SEG_U8 = constants("SEG_F32", "SEG_BF16", "SEG_U8")   # element kinds of fz_seg_counts
+LABEL_U8, LABEL_I64, LABEL_F32 = constants("LABEL_U8", "LABEL_I64", "LABEL_F32")   # element kinds of a class-index label map
+VOL_F32, VOL_BF16, VOL_U8, VOL_I16 = constants("VOL_F32", "VOL_BF16", "VOL_U8", "VOL_I16")
+VOL_IMAGE_IN, VOL_IMAGE_OUT, VOL_LABEL_IN, VOL_LOGITS = constants("VOL_ROLE_IMAGE_IN", "VOL_ROLE_IMAGE_OUT", "VOL_ROLE_LABEL_IN",
+                                                                  "VOL_ROLE_LOGITS")
+RESPACE_BILINEAR, RESPACE_NEAREST = constants("RESPACE_BILINEAR", "RESPACE_NEAREST")
+DROP_RES, DROP_GELU, DROP_GELU_BWD = constants("DROP_RES", "DROP_GELU", "DROP_GELU_BWD")
 _products = threading.local()   # per thread: two models driven from two threads may use different pipes
 
 
@@ -93,24 +115,63 @@ _lock = threading.Lock()
 _lib = None
 
 _c = ctypes
-_vp, _i, _i64, _f = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float
+_i = _c.c_int
+_SCALARS = {"int": _i, "int64_t": _c.c_int64, "float": _c.c_float, "double": _c.c_double}
 
-_SIGS = {
-    "fz_version": ([], _i),
-    "fz_abi_version": ([], _i),
-    "fz_set_tile_order": ([_i], _i),
-    "fz_last_error_string": ([], _c.c_char_p),
-    "fz_launch_count": ([], _i64),
-    "fz_swm_fwd": ([_vp, _vp] + [_i] * 10 + [_c.POINTER(_i), _i, _i, _i, _vp], _i),
-    "fz_swm_inv": ([_vp, _vp] + [_i] * 10 + [_c.POINTER(_i), _i, _vp, _i, _vp], _i),
-    "fz_nmf_fwd": ([_vp] * 6 + [_i64] + [_i] * 5 + [_f, _i, _vp], _i),
-    "fz_nmf_bwd": ([_vp] * 7 + [_i64] + [_i] * 6 + [_f, _i, _vp], _i),
-    "fz_nmf_supported": ([_i] * 5, _i),
+
+def _ctype(t, where):
+    """ctypes type of a header type, by the rules at the top of include/factorizer_hip.h"""
+    if t.base in _H.structs:
+        return _c.POINTER(_DESC[t.base]) if t.ptr == 1 else _c.POINTER(_c.POINTER(_DESC[t.base]))
+    if t.ptr == 0:
+        return _SCALARS.get(t.base, _c.c_void_p)           # fz_stream_t
+    if t.ptr == 2:
+        return _c.POINTER(_c.c_void_p)                     # host array of device pointers
+    if t.base == "int":
+        return _c.POINTER(_i)                              # host array
+    if t.base == "char":                                   # only as the `const char*` a function returns
+        raise NativeError(f"{where}: a char* needs an entry in _ARG_EXCEPTIONS (factorizer_amd/_native.py)")
+    return _c.c_void_p                                     # device buffer
+
+
+_FIELD_NAMES = {("fz_mlp_desc", "in"): "inp"}   # `in` is a Python keyword: d.in = ... does not parse
+
+
+def _descriptor(name):
+    """ctypes.Structure of a header struct, named like it: fz_gemm_dw_desc -> GemmDwDesc"""
+    fields = [(_FIELD_NAMES.get((name, f), f), _ctype(t, f"{name}.{f}") * n if n else _ctype(t, f"{name}.{f}"))
+              for t, f, n in _H.structs[name]]
+    return type("".join(p.title() for p in name.split("_")[1:]), (_c.Structure,), {"_fields_": fields})
+
+
+_DESC = {}
+for _name in _H.structs:   # in the header's order: a field may point to a struct declared before its own
+    _DESC[_name] = _descriptor(_name)
+GemmDesc, MlpDesc, MlpDropout, GemmDwDesc, OutprojFac = (_DESC["fz_" + n] for n in (
+    "gemm_desc", "mlp_desc", "mlp_dropout", "gemm_dw_desc", "outproj_fac"))
+BlockPrologue, WgradDesc, VolGeom, RespaceGeom = (_DESC["fz_" + n] for n in (
+    "block_prologue", "wgrad_desc", "vol_geom", "respace_geom"))
+
+_ARG_EXCEPTIONS = {
+    # a HOST array of up to 8 bytes that the launcher reads before the launch; by the rules a uint8_t* is a device buffer
+    ("fz_vol_restore", "label_values"): _c.POINTER(_c.c_ubyte),
+    # a HOST character buffer of `cap` bytes that the dry run writes the kernel form's name into
+    ("fz_gemm_plan", "form"): _c.c_char_p,
 }
 
 
-class NativeError(RuntimeError):
-    pass
+def _signatures():
+    """{entry point: (argtypes, restype)} of every prototype of the header"""
+    sigs = {name: ([_ARG_EXCEPTIONS.get((name, a)) or _ctype(t, f"{name}, argument `{a}`") for t, a in args],
+                   _c.c_char_p if ret == ("char", 1) else _ctype(ret, f"{name}, return type"))
+            for name, (ret, args) in _H.functions.items()}
+    stale = set(_ARG_EXCEPTIONS) - {(name, a) for name, (_, args) in _H.functions.items() for _, a in args}
+    if stale:   # an argument renamed in the header would otherwise fall back to its rule in silence
+        raise NativeError(f"_ARG_EXCEPTIONS names {sorted(stale)}, which include/factorizer_hip.h does not declare")
+    return sigs
+
+
+_SIGS = _signatures()
 
 
 def declared_symbols():
@@ -136,8 +197,9 @@ def lib():
         except AttributeError:
             abi = None
         if abi != ABI_VERSION:
-            raise NativeError(f"{LIB_PATH} has ABI revision {abi}, this binding is written against {ABI_VERSION} "
-                              "(include/factorizer_hip.h: FZ_ABI_VERSION): rebuild with `python -m factorizer_amd.build`")
+            raise NativeError(f"{LIB_PATH} has ABI revision {abi} and was not built from this tree's include/factorizer_hip.h "
+                              f"(FZ_ABI_VERSION {ABI_VERSION}), which the binding is derived from: rebuild with "
+                              "`python -m factorizer_amd.build`")
         for name, (args, res) in _SIGS.items():
             fn = getattr(h, name)  # AttributeError if the .so does not export it
             fn.argtypes = args
@@ -169,25 +231,6 @@ def shifts_array(shifts):
     return (_i * len(flat))(*flat)
 
 
-# ---- descriptor structs of the GEMM family (include/factorizer_hip.h) -----------------------
-_fp = _c.POINTER(_c.c_float)
-
-
-class GemmDesc(_c.Structure):
-    _fields_ = [("x", _vp * 4), ("nsrc", _i), ("src_mode", _i), ("c0", _i), ("Cin", _i), ("Vin", _i64),
-                ("Di", _i), ("Hi", _i), ("Wi", _i), ("w", _vp), ("w_t", _i), ("ldw", _i), ("M", _i), ("K", _i),
-                ("bias", _vp), ("ln", _i), ("ln_g", _vp), ("ln_b", _vp), ("ln_eps", _f), ("stats_out", _vp),
-                ("bact", _i), ("bmul", _vp), ("bmul_kind", _i), ("eact", _i), ("res", _vp), ("emul", _vp), ("emul_kind", _i), ("y", _vp),
-                ("Ncol", _i64), ("Ho", _i), ("Wo", _i), ("B", _i), ("loader", _i), ("epilogue", _i), ("lnb_x", _vp), ("lnb_stats", _vp), ("lnb_g", _vp),
-                ("lnb_gadd", _vp), ("lnb_part", _vp), ("act_dtype", _i), ("products", _i), ("tune", _i)]
-
-
-class OutprojFac(_c.Structure):
-    """fz_outproj_fac (include/factorizer_hip.h): the core's output as the rank-1 factors of its two windows, for
-    fz_mlp_chain_fac / fz_gemm_dw_fac"""
-    _fields_ = [("v", _vp * 2), ("u", _vp * 2), ("dims", _i * 3), ("heads", _i), ("shift", _i * 6)]
-
-
 def outproj_fac(fac, geo):
     """fz_outproj_fac of fac = (vfac0, ufac0, vfac1, ufac1) (functional.core_factors) on geometry `geo`"""
     d = OutprojFac()
@@ -196,203 +239,3 @@ def outproj_fac(fac, geo):
     d.heads = geo.h
     d.shift[:] = [int(v) for s in geo.shifts3 for v in s]
     return d
-
-
-class MlpDesc(_c.Structure):
-    _fields_ = [("mode", _i), ("inp", _vp), ("w1", _vp), ("w2", _vp), ("b1", _vp), ("b2", _vp), ("ln_g", _vp),
-                ("ln_b", _vp), ("ln_eps", _f), ("stats", _vp), ("z1", _vp), ("gz1", _vp), ("x1", _vp), ("out", _vp),
-                ("part", _vp), ("B", _i), ("C", _i), ("H", _i), ("V", _i64), ("act_dtype", _i), ("wpart", _vp),
-                ("gw1", _vp), ("gb1", _vp), ("gw2", _vp), ("gb2", _vp), ("gln", _vp), ("glp", _vp), ("products", _i),
-                ("pre_in", _vp), ("pre_w", _vp), ("pre_b", _vp), ("pre_res", _vp), ("pre_out", _vp),
-                ("post_w", _vp), ("post_b", _vp), ("post_out", _vp), ("post_m", _i)]
-
-
-class MlpDropout(_c.Structure):
-    """fz_mlp_dropout (include/factorizer_hip.h): the block's dropout planes and scales for fz_mlp_chain_drop"""
-    _fields_ = [("m0", _vp), ("m1", _vp), ("m2", _vp), ("s0", _f), ("s1", _f), ("s2", _f)]
-
-
-class BlockPrologue(_c.Structure):
-    """fz_block_prologue (include/factorizer_hip.h)"""
-    _fields_ = [("ln_g", _vp), ("ln_b", _vp), ("ln_eps", _f), ("w", _vp), ("t", _vp), ("stats", _vp)]
-
-
-class GemmDwDesc(_c.Structure):
-    _fields_ = [("g", _vp), ("q", _vp), ("w", _vp), ("ln", _i), ("stats", _vp), ("ln_g", _vp), ("ln_b", _vp), ("gadd", _vp),
-                ("y", _vp), ("gln", _vp), ("wpart", _vp), ("gw", _vp), ("gb", _vp), ("B", _i), ("C", _i), ("V", _i64),
-                ("act_dtype", _i), ("ldgw", _i), ("ldw", _i), ("drop_m", _vp), ("drop_s", _f)]
-
-
-class WgradDesc(_c.Structure):
-    _fields_ = [("p", _vp), ("M", _i), ("pmul", _vp), ("pmul_kind", _i), ("q", _vp * 4), ("nsrc", _i),
-                ("src_mode", _i), ("c0", _i), ("Cin", _i), ("K", _i), ("Vq", _i64), ("D", _i), ("H", _i),
-                ("W", _i), ("N", _i64), ("Ho", _i), ("Wo", _i), ("stats", _vp), ("qact", _i), ("ln_g", _vp),
-                ("ln_b", _vp), ("gw", _vp), ("gbias", _vp), ("accumulate", _i), ("B", _i), ("loader", _i),
-                ("act_dtype", _i), ("products", _i)]
-
-
-class VolGeom(_c.Structure):
-    """fz_vol_geom (include/factorizer_hip.h): axes lifted to three, z, y, x"""
-    _fields_ = [("nd", _i), ("size", _i * 3), ("start", _i * 3), ("end", _i * 3), ("pad", _i * 3), ("out", _i * 3)]
-
-
-class RespaceGeom(_c.Structure):
-    """fz_respace_geom (include/factorizer_hip.h): axes lifted to three, z, y, x"""
-    _fields_ = [("nd", _i), ("src_size", _i * 3), ("src_axis", _i * 3), ("flip", _i * 3), ("res_size", _i * 3), ("pad", _i * 3),
-                ("out", _i * 3), ("orig_size", _i * 3), ("box_start", _i * 3), ("scale", _c.c_double * 3),
-                ("inv_scale", _c.c_double * 3)]
-
-
-def _wide_nmf_sigs(fam):
-    """the entry points that the two split-N NMF families have alike (csrc/nmf_wide.h): the fp32 ones, and the `_act` ones with
-    act_dtype before the workspace"""
-    shape = [_i64, _i, _i64, _i, _i]                 # nmat M N R T
-    fwd = [_vp] * 6 + shape + [_i, _f]               # x u0 v0 y u_out v_out | shape | solver eps
-    bwd = [_vp] * 7 + shape + [_i, _i, _f]           # x u0 v0 gy gu gv gx | shape | Tgrad solver eps
-    out = {f"fz_{fam}_supported": ([_i, _i64, _i, _i, _i], _i)}
-    for sfx, act in (("", []), ("_act", [_i])):
-        out[f"fz_{fam}_workspace_bytes{sfx}"] = (shape + [_i] + act, _i64)          # ... backward [act_dtype]
-        out[f"fz_{fam}_fwd{sfx}"] = (fwd + act + [_vp, _vp], _i)                    # ... [act_dtype] workspace stream
-        out[f"fz_{fam}_bwd{sfx}"] = (bwd + act + [_vp, _vp], _i)
-    return out
-
-
-_SIGS.update({
-    "fz_gcorr_supported": ([_i] * 5, _i),
-    "fz_gcorr": ([_vp] * 5 + [_i] * 11 + [_f, _vp], _i),
-    "fz_gcorr_wgrad_workspace_bytes": ([_i] * 10, _i64),
-    "fz_gcorr_wgrad": ([_vp] * 4 + [_i] * 11 + [_vp], _i),
-    "fz_gcorr_act": ([_vp] * 5 + [_i] * 11 + [_f, _i, _vp], _i),
-    "fz_gcorr_wgrad_act": ([_vp] * 4 + [_i] * 12 + [_vp], _i),
-    "fz_gcorr_mu_bwd": ([_vp] * 8 + [_i] * 11 + [_f, _i, _vp], _i),
-    "fz_gnmf_launches": ([_i, _i, _i], _i),
-    "fz_gnmfx_launches": ([_i, _i64, _i, _i, _i, _i], _i),
-    **_wide_nmf_sigs("gnmf"),
-    **_wide_nmf_sigs("gnmfx"),
-    "fz_nmf_cf_supported": ([_i] * 11, _i),
-    "fz_nmf_cf_fwd": ([_vp] * 4 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 5 + [_f, _i, _vp], _i),
-    "fz_nmf_cf_bwd": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 7 + [_f, _i, _vp], _i),
-    "fz_nmf_cf_factors_supported": ([_i] * 12 + [_c.POINTER(_i)], _i),
-    "fz_nmf_cf_factors_to_tensor": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] * 2 + [_i, _vp], _i),
-    "fz_outproj_factors_supported": ([_i] * 13 + [_c.POINTER(_i)] + [_i] * 3, _i),
-    "fz_nmf_cf_fwd_store_factors": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 3 + [_f, _i, _vp], _i),
-    "fz_nmf_cf_fwd_from_factors": ([_vp] * 6 + [_i] * 5 + [_c.POINTER(_i)] * 2 + [_i] * 4 + [_f, _i, _vp], _i),
-    "fz_nmf_cf_bwd_factors_supported": ([_i] * 14 + [_c.POINTER(_i)], _i),
-    "fz_nmf_cf_bwd_store_factors": ([_vp] * 5 + [_i] * 5 + [_c.POINTER(_i)] + [_i] * 3 + [_f, _i, _vp], _i),
-    "fz_nmf_cf_bwd_from_factors": ([_vp] * 6 + [_i] * 5 + [_c.POINTER(_i)] * 2 + [_i] * 3 + [_f, _i, _vp], _i),
-    "fz_nmf_pcf_supported": ([_i] * 11, _i),
-    "fz_nmf_pcf_fwd": ([_vp] * 4 + [_i] * 8 + [_c.POINTER(_i)] + [_i] * 5 + [_f, _i, _vp], _i),
-    "fz_nmf_pcf_bwd": ([_vp] * 5 + [_i] * 8 + [_c.POINTER(_i)] + [_i] * 7 + [_f, _i, _vp], _i),
-    "fz_nmf_pcf_bwd_prefers_separate": ([_i] * 4, _i),
-    "fz_act_add": ([_vp, _vp, _i64, _i, _vp], _i),
-    "fz_mlp_pre_supported": ([_i, _i, _i64, _i], _i),
-    "fz_mlp_drop_supported": ([_i, _i, _i64, _i], _i),
-    "fz_mlp_chain_drop": ([_c.POINTER(MlpDesc), _c.POINTER(MlpDropout), _vp], _i),
-    "fz_mlp_chain_fac": ([_c.POINTER(MlpDesc), _c.POINTER(OutprojFac), _vp], _i),
-    "fz_gemm_dw_fac": ([_c.POINTER(GemmDwDesc), _c.POINTER(OutprojFac), _vp], _i),
-    "fz_conv3_prologue_supported": ([_i] * 4, _i),
-    "fz_conv3_fwd2": ([_vp] * 4 + [_i] * 8 + [_c.POINTER(BlockPrologue), _vp], _i),
-    "fz_upcat2": ([_vp, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_c.POINTER(BlockPrologue), _vp], _i),
-    "fz_gemm": ([_c.POINTER(GemmDesc), _vp], _i),
-    "fz_gemm_plan": ([_c.POINTER(GemmDesc), _c.c_char_p, _i], _i),
-    "fz_gemm_bx_enable": ([_i], _i),
-    "fz_gemm_lnbwd_partials": ([_c.POINTER(GemmDesc)], _i64),
-    "fz_reduce_rows": ([_vp, _i64, _i, _vp, _vp, _vp], _i),
-    "fz_adamw_step": ([_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp], _i),
-    "fz_sw_gather": ([_vp, _vp] + [_i] * 10 + [_vp], _i),
-    "fz_sw_accumulate": ([_vp] * 6 + [_f] + [_i] * 10 + [_vp], _i),
-    "fz_sw_finalize": ([_vp, _vp, _i, _i64, _vp], _i),
-    "fz_sw_gather2": ([_vp, _vp] + [_i] * 11 + [_vp], _i),
-    "fz_sw_accumulate2": ([_vp] * 6 + [_f] + [_i] * 11 + [_vp], _i),
-    "fz_sw_finalize2": ([_vp, _vp, _vp, _i, _i64, _i, _vp], _i),
-    "fz_mlp_supported": ([_i, _i, _i64], _i),
-    "fz_mlp_partials": ([_i, _i64], _i64),
-    "fz_mlp_wgrad_rows": ([_i, _i64], _i),
-    "fz_gemm_dw_rows": ([_i, _i64], _i),
-    "fz_gemm_dw_workspace_bytes": ([_i, _i64], _i64),
-    "fz_gemm_dw": ([_c.POINTER(GemmDwDesc), _vp], _i),
-    "fz_mlp_wgrad_workspace_bytes": ([_i, _i64], _i64),
-    "fz_mlp_chain": ([_c.POINTER(MlpDesc), _vp], _i),
-    "fz_head_bwd_rows": ([], _i),
-    "fz_head_bwd_workspace_bytes": ([], _i64),
-    "fz_head_bwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp], _i),
-    "fz_head_fwd": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp], _i),
-    "fz_upcat_supported": ([_i] * 5, _i),
-    "fz_upcat_compose": ([_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
-    "fz_upcat_wgrads": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp], _i),
-    "fz_upcat": ([_vp, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_vp], _i),
-    "fz_upcat_bwd_supported": ([_i] * 6, _i),
-    "fz_upcat_bwd_workspace_bytes": ([_i] * 4, _i64),
-    "fz_upcat_bwd": ([_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp] + [_i] * 7 + [_vp], _i),
-    "fz_wgrad": ([_c.POINTER(WgradDesc), _vp, _vp], _i),
-    "fz_wgrad_group": ([_c.POINTER(_c.POINTER(WgradDesc)), _c.POINTER(_vp), _i, _vp], _i),
-    "fz_wgrad_workspace_bytes": ([_c.POINTER(WgradDesc)], _i64),
-    "fz_conv3_fwd": ([_vp] * 4 + [_i] * 8 + [_vp], _i),
-    "fz_conv3_wgrad_chunks": ([_i] * 4, _i),
-    "fz_conv3_wgrad_partials": ([_vp] * 4 + [_i] * 8 + [_vp], _i),
-    "fz_chunk_reduce": ([_vp, _i, _i64, _vp, _i, _vp], _i),
-    "fz_chunk_reduce_ld": ([_vp, _i, _i64, _i64, _vp, _i, _vp], _i),
-    "fz_finish_defer": ([_i], _i),
-    "fz_finish_pending": ([], _i),
-    "fz_finish_flush": ([_vp], _i),
-    "fz_finish_flush_all": ([_vp], _i),
-    "fz_dice_bce_chunks": ([_i64], _i),
-    "fz_dice_bce_sums": ([_vp, _vp, _vp, _i, _i64, _vp], _i),
-    "fz_dice_bce_grad": ([_vp, _vp, _vp, _vp, _i, _i64, _f, _f, _vp, _vp], _i),
-    "fz_dice_ce_sums": ([_vp, _vp, _vp, _i, _i, _i64, _vp], _i),
-    "fz_dice_ce_grad": ([_vp, _vp, _vp, _vp, _i, _i, _i64, _f, _f, _vp, _vp], _i),
-    "fz_dice_ce_finish": ([_vp, _i, _i, _i64, _f, _vp, _vp, _vp], _i),
-    "fz_dice_bce_ds_sums": ([_vp, _vp, _vp, _i] + [_i] * 6 + [_i, _vp], _i),
-    "fz_dice_bce_ds_grad": ([_vp, _vp, _vp, _vp, _i] + [_i] * 6 + [_i, _f, _f, _vp, _vp], _i),
-    "fz_dice_ce_ds_sums": ([_vp, _vp, _vp, _i, _i] + [_i] * 6 + [_i, _vp], _i),
-    "fz_dice_ce_ds_grad": ([_vp, _vp, _vp, _vp, _i, _i] + [_i] * 6 + [_i, _f, _f, _vp, _vp], _i),
-    "fz_dice_sce_sums": ([_vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp], _i),
-    "fz_dice_sce_finish": ([_vp, _i, _i, _i64, _i, _f, _vp, _vp, _vp], _i),
-    "fz_dice_sce_grad": ([_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _i, _f, _f, _vp, _vp], _i),
-    "fz_dice_sce_ds_sums": ([_vp, _vp, _vp, _i, _i] + [_i] * 6 + [_i, _i, _vp], _i),
-    "fz_dice_sce_ds_grad": ([_vp, _vp, _vp, _vp, _i, _i] + [_i] * 6 + [_i, _i, _i, _f, _f, _vp, _vp], _i),
-    "fz_rowsum_chunks": ([_i64], _i),
-    "fz_rowsum": ([_vp, _vp, _vp, _i, _i, _i64, _i, _vp], _i),
-    "fz_ln_fwd": ([_vp] * 5 + [_i, _i, _i64, _f, _i, _vp], _i),
-    "fz_ln_bwd": ([_vp] * 8 + [_i, _i, _i64, _i, _vp], _i),
-    "fz_ln_bwd_workspace_bytes": ([_i], _i64),
-    "fz_ln_bwd_workspace_bytes2": ([_i, _i, _i64], _i64),
-    "fz_dropout_bits_words": ([_i, _i, _i64], _i64),
-    "fz_dropout_keep_bits": ([_vp, _i, _i, _i, _i64, _f, _vp, _vp], _i),
-    "fz_dropout_apply": ([_i, _vp, _f, _vp, _vp, _vp, _i, _i, _i64, _i, _vp], _i),
-    "fz_seg_counts_chunks": ([_i64], _i),
-    "fz_seg_counts_workspace_bytes": ([_i, _i64], _i64),
-    "fz_seg_counts": ([_vp, _i, _vp, _i, _f, _vp, _vp, _vp, _i, _i64, _vp], _i),
-    "fz_mask_edges": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
-    "fz_edge_min_dist2_splits": ([_i64, _i64], _i),
-    "fz_edge_min_dist2_workspace_bytes": ([_i64, _i64], _i64),
-    "fz_edge_min_dist2": ([_vp, _i64, _vp, _i64, _f, _f, _f, _vp, _vp, _vp], _i),
-    "fz_seg_argmax_workspace_bytes": ([_i, _i, _i64], _i64),
-    "fz_seg_argmax": ([_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp], _i),
-    "fz_aug_record_floats": ([], _i),
-    "fz_aug_resample": ([_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp], _i),
-    "fz_aug_smooth": ([_vp, _vp, _i, _i, _vp, _vp] + [_i] * 6 + [_vp], _i),
-    "fz_aug_noise_field": ([_vp, _vp, _i, _i, _i64, _vp], _i),
-    "fz_aug_source_words": ([], _i),
-    "fz_aug_crop_resample": ([_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp], _i),
-    "fz_vol_kind_ok": ([_i, _i], _i),
-    "fz_vol_bbox": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
-    "fz_vol_workspace_bytes": ([_i, _c.POINTER(VolGeom)], _i64),
-    "fz_vol_stats": ([_vp, _i, _i, _c.POINTER(VolGeom), _i, _i, _vp, _vp], _i),
-    "fz_vol_write": ([_vp, _i, _vp, _i, _i, _vp, _i, _i, _c.POINTER(_i), _c.POINTER(_i), _i, _vp, _c.POINTER(VolGeom), _i, _i,
-                      _vp, _vp, _vp, _vp], _i),
-    "fz_vol_restore": ([_c.POINTER(_vp), _i, _i, _i, _c.POINTER(VolGeom), _f, _c.POINTER(_c.c_ubyte), _vp, _vp], _i),
-    "fz_vol_respace": ([_vp, _i, _vp, _i, _vp, _i, _vp, _c.POINTER(RespaceGeom), _i, _vp], _i),
-    "fz_vol_unspace": ([_c.POINTER(_vp), _i, _i, _i, _c.POINTER(RespaceGeom), _i, _i, _f, _vp, _vp], _i),
-    "fz_inorm_one_pass_max": ([], _i),
-    "fz_inorm_chunks": ([_i64], _i),
-    "fz_inorm_workspace_bytes": ([_i64, _i64], _i64),
-    "fz_inorm_fwd": ([_vp] * 5 + [_i64, _i, _i64, _c.c_double, _i, _vp, _vp], _i),
-    "fz_inorm_bwd": ([_vp] * 7 + [_i64, _i, _i64, _i, _vp, _vp], _i),
-})
-SEG_F32, SEG_BF16, SEG_U8 = 0, 1, 2   # include/factorizer_hip.h: FZ_SEG_* element kinds of fz_seg_counts
-LABEL_U8, LABEL_I64, LABEL_F32 = 0, 1, 2   # FZ_LABEL_*: element kinds of a class-index label map
-VOL_F32, VOL_BF16, VOL_U8, VOL_I16 = 0, 1, 2, 3   # include/factorizer_hip.h: FZ_VOL_* element kinds
-VOL_IMAGE_IN, VOL_IMAGE_OUT, VOL_LABEL_IN, VOL_LOGITS = 0, 1, 2, 3   # FZ_VOL_ROLE_*
-RESPACE_BILINEAR, RESPACE_NEAREST = 0, 1   # FZ_RESPACE_*
-DROP_RES, DROP_GELU, DROP_GELU_BWD = 0, 1, 2   # include/factorizer_hip.h: FZ_DROP_*

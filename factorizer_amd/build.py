@@ -11,6 +11,8 @@ import shutil
 import subprocess
 import sys
 
+from ._header import INCLUDE_DIR
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "build")
@@ -55,7 +57,7 @@ def sources():
 
 def _newest(suffixes) -> float:
     m = 0.0
-    for root in (CSRC, os.path.join(os.path.dirname(HERE), "include")):
+    for root in (CSRC, INCLUDE_DIR):
         for f in os.listdir(root):
             if f.endswith(suffixes):
                 m = max(m, os.path.getmtime(os.path.join(root, f)))

@@ -26,10 +26,10 @@ from . import _native as N
 from . import gradbuf as _GB
 from . import functional as Fn
 
-ACT = {"none": 0, "relu": 1, "gelu": 2}
-LOAD_PLAIN, LOAD_S2D, LOAD_K3, LOAD_S2D_2D, LOAD_K3_2D = 0, 1, 2, 3, 4
-EPI_PLAIN, EPI_D2S, EPI_LNBWD, EPI_D2S_2D = 0, 1, 2, 3
-QL_S2D_2D, QL_K3_2D = LOAD_S2D_2D, LOAD_K3_2D   # fz_wgrad's own names of the two ids (FZ_QL_* in the header): nothing here passes them
+ACT = dict(zip(("none", "relu", "gelu"), N.constants("ACT_NONE", "ACT_RELU", "ACT_GELU")))
+LOAD_PLAIN, LOAD_S2D, LOAD_K3, LOAD_S2D_2D, LOAD_K3_2D = N.constants("LOAD_PLAIN", "LOAD_S2D", "LOAD_K3", "LOAD_S2D_2D", "LOAD_K3_2D")
+EPI_PLAIN, EPI_D2S, EPI_LNBWD, EPI_D2S_2D = N.constants("EPI_PLAIN", "EPI_D2S", "EPI_LNBWD", "EPI_D2S_2D")
+QL_S2D_2D, QL_K3_2D = N.constants("QL_S2D_2D", "QL_K3_2D")   # fz_wgrad's own names of the two loader ids: nothing here passes them
 _D2S_FINE = {EPI_D2S: 8, EPI_D2S_2D: 4}   # fine voxels per coarse column of a depth-to-space epilogue
 
 

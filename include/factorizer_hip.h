@@ -15,6 +15,22 @@
  *     error string, the `products` default (fz_set_products), the tile order (fz_set_tile_order), the defer flag
  *     (fz_finish_defer).  Nothing else outlives a call.
  *   - tensors are dense, contiguous, row-major ("channels-first": B,C,D,H,W).
+ *
+ * This header is the only statement of the ABI: factorizer_amd/_header.py reads it and factorizer_amd/_native.py derives the
+ * ctypes binding (argument lists, descriptor layouts, constants) from what it reads.  It refuses a declaration that it has no
+ * rule for, so declarations keep to these forms: `#define FZ_NAME <integer>` or `(<-integer>)`; `typedef struct fz_x { ... }
+ * fz_x;` with fields `T a;`, `T a, b;` or `T a[N];`; `RET fz_name(T a, ...);` with RET one of int, int64_t, const char*.
+ * How a type is bound:
+ *   int, int64_t, float, double                            the scalar
+ *   fz_stream_t                                            an opaque pointer
+ *   const char* (return)                                   a C string
+ *   pointer to a struct of this header                     pointer to that descriptor
+ *   pointer to void or float                               DEVICE buffer: an opaque pointer
+ *   pointer to uint8_t, int32_t, uint32_t, int64_t, double DEVICE buffer: an opaque pointer
+ *   int*, const int*                                       HOST array of int
+ *   pointer to pointer                                     HOST array of opaque pointers / of descriptor pointers
+ * A fixed-width element type therefore says "device memory" and plain int says "host memory".  The arguments that do not
+ * follow this are listed one by one, each with its reason, in factorizer_amd/_native.py (_ARG_EXCEPTIONS).
  */
 #ifndef FACTORIZER_HIP_H
 #define FACTORIZER_HIP_H

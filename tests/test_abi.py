@@ -3,6 +3,8 @@ include/factorizer_hip.h declares (no compute calls — there is no GPU in this 
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -43,6 +45,104 @@ def test_python_binding_matches_header(built_lib):
     assert lib.fz_version() >= 100
     assert lib.fz_abi_version() == _native.ABI_VERSION   # the loader refuses a library of another revision
     assert lib.fz_last_error_string() is not None
+
+
+def test_binding_covers_every_entry_point():
+    """the binding is derived from the header: no entry point is missing from it and none is bound that the header lacks"""
+    from factorizer_amd import _native
+    assert set(_native.declared_symbols()) == set(header_functions())
+    assert len(_native.declared_symbols()) > 100
+
+
+def test_descriptor_layouts_match_the_c_compiler(tmp_path):
+    """sizeof and every offsetof of the header's structs, as the host C compiler lays them out, against the ctypes classes"""
+    from factorizer_amd import _header, _native
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("no host C compiler")
+    structs = _header.read().structs
+    assert len(structs) >= 9
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "factorizer_hip.h"', "int main(void) {"]
+    for name, fields in structs.items():
+        lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'  printf("{name}.{f} %zu\\n", offsetof({name}, {f}));' for _, f, _ in fields]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["  return 0;", "}"]) + "\n")
+    subprocess.run([cc, "-I", _header.INCLUDE_DIR, "-o", str(tmp_path / "layout"), str(src)], check=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
+    compiled = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    bound = {}
+    for name, fields in structs.items():
+        cls = _native._DESC[name]
+        assert len(cls._fields_) == len(fields), name
+        bound[name] = ctypes.sizeof(cls)
+        for (_, f, _), (pyname, _) in zip(fields, cls._fields_):   # positional: fz_mlp_desc.in is `inp` in Python
+            bound[f"{name}.{f}"] = getattr(cls, pyname).offset
+    assert bound == compiled
+
+
+def _parse_error(text):
+    from factorizer_amd import _header
+    with pytest.raises(_header.NativeError) as e:
+        _header.parse(text)
+    return str(e.value)
+
+
+def test_header_reader_on_snippets():
+    from factorizer_amd import _header
+    T = _header.CType
+    h = _header.parse("""
+        /* a comment with ; and ( in it: fz_not_a_function(int x); */
+        #ifndef GUARD_H
+        #define GUARD_H
+        #define FZ_ZERO 0
+        #define FZ_E_BAD (-3) /* ; ( */
+        typedef void* fz_stream_t; // hipStream_t; fz_neither(
+        struct fz_geom;
+        typedef struct fz_geom {
+          int Di, Hi, Wi;       /* multi-declarator; */
+          const void* x[4];
+          double scale[3];
+          int64_t V;
+          const uint32_t* bits;
+        } fz_geom;
+        int fz_version(void);
+        const char* fz_text(void);
+        int64_t fz_three_lines(const void* x /* activation */, const int* shifts,
+                               const struct fz_geom* geom, float eps,
+                               fz_stream_t stream);
+        int fz_group(const fz_geom* const* descs, void* const* workspaces, int n);
+        #endif
+    """)
+    assert h.defines == {"FZ_ZERO": 0, "FZ_E_BAD": -3}
+    assert h.structs == {"fz_geom": [(T("int", 0), "Di", 0), (T("int", 0), "Hi", 0), (T("int", 0), "Wi", 0), (T("void", 1), "x", 4),
+                                     (T("double", 0), "scale", 3), (T("int64_t", 0), "V", 0), (T("uint32_t", 1), "bits", 0)]}
+    assert list(h.functions) == ["fz_version", "fz_text", "fz_three_lines", "fz_group"]
+    assert h.functions["fz_version"] == (T("int", 0), [])
+    assert h.functions["fz_text"] == (T("char", 1), [])
+    assert h.functions["fz_three_lines"] == (T("int64_t", 0), [(T("void", 1), "x"), (T("int", 1), "shifts"), (T("fz_geom", 1), "geom"),
+                                                               (T("float", 0), "eps"), (T("fz_stream_t", 0), "stream")])
+    assert h.functions["fz_group"] == (T("int", 0), [(T("fz_geom", 2), "descs"), (T("void", 2), "workspaces"), (T("int", 0), "n")])
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int fz_f(size_t n);", ["fz_f", "size_t"]),                              # a type without a rule
+    ("int fz_f(unsigned n);", ["fz_f", "unsigned"]),
+    ("int fz_f(const float*** p);", ["fz_f", "float***"]),
+    ("void* fz_f(int n);", ["fz_f"]),                                         # a return type without a rule
+    ("typedef struct fz_s { short a; } fz_s;", ["fz_s", "short"]),
+    ("typedef struct fz_s { int (*cb)(int); } fz_s;", ["fz_s", "cb"]),        # a field that does not fit
+    ("typedef struct fz_s { int a : 3; } fz_s;", ["fz_s", "a : 3"]),
+    ("static inline int fz_x(int a) { return a; }", ["fz_x"]),                # fz_x( left over: not a prototype
+    ("int fz_a(int x), fz_b(int y);", ["fz_a"]),
+    ("int fz_f(int n); int fz_f(int n);", ["fz_f"]),                          # declared twice
+    ("#define FZ_N 1u", ["FZ_N"]),                                            # a constant that is not an integer
+    ("#define FZ_CALL(x) fz_x(x)", ["FZ_CALL"]),
+    ("struct fz_unknown;", ["fz_unknown"]),
+])
+def test_header_reader_refuses(text, names):
+    msg = _parse_error(text)
+    assert all(n in msg for n in names), msg
 
 
 def test_host_side_argument_checks(built_lib):

@@ -13,6 +13,8 @@ from .nmf import (NMF, SVD, BCDSolver, Compose, CoordinateDescent, FastMultiplic
 from .layers import MLP, LayerNorm, Linear, PosEmbed, PositionalEmbedding
 from .convs import Conv2d, Conv3d, ConvTranspose2d, ConvTranspose3d
 from .instance_norm import InstanceNorm1d, InstanceNorm2d, InstanceNorm3d, convert_instance_norm, instance_norm
+from .group_norm import GroupNorm, convert_group_norm, group_norm
+from .cnn import BasicBlock, DoubleConv, PreActivationBlock, SepConv
 from .blocks import FactMixer, FactorizerBlock, FactorizerStage
 from .losses import (DeepSupervisionLoss, DiceCELoss, deep_supervision_loss, dice_bce_loss, dice_ce_loss,
                      dice_ce_softmax_loss, dice_ce_softmax_loss_composed)

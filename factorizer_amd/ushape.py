@@ -17,6 +17,7 @@ from torch import nn
 
 from . import convs
 from .blocks import FactorizerStage
+from .cnn import DoubleConv
 from .layers import PositionalEmbedding
 from .utils import as_tuple, partialize
 
@@ -58,10 +59,7 @@ class UNetStage(nn.Module):
 
     def __init__(self, in_channels, out_channels, depth=1, block=None, **kwargs):
         super().__init__()
-        if block is None:
-            raise ValueError("UNetStage needs a `block` (the reference's CNN DoubleConv default is outside "
-                             "this build's scope)")
-        make = partialize(block)
+        make = partialize(DoubleConv if block is None else block)   # (unet.py:23)
         layers = [make(in_channels, out_channels, **kwargs)]
         layers += [make(out_channels, out_channels, **kwargs) for _ in range(depth - 1)]
         self.blocks = nn.Sequential(*layers)
@@ -178,8 +176,6 @@ class UNet(nn.Module):
                  strides=(1, 2, 2, 2, 2), decoder_depth=(1, 1, 1, 1), stem=None, downsample=None,
                  block=None, upsample=None, head=None, num_deep_supr=False, **kwargs):
         super().__init__()
-        if block is None:
-            raise ValueError("UNet needs a `block` spec per stage (Factorizer supplies FactorizerStage)")
         self.spatial_dims = spatial_dims
         self.spatial_size = spatial_size
         n_enc, n_dec = len(encoder_depth), len(decoder_depth)
@@ -192,6 +188,8 @@ class UNet(nn.Module):
         downsample = downsample or (conv, {"kernel_size": 2})
         upsample = upsample or (tconv, {"kernel_size": 2})
         head = head or (conv, {"kernel_size": 1})
+        if block is None:   # the reference's CNN U-Net (unet.py:215-220)
+            block = Same((DoubleConv, {"conv": (conv, {"kernel_size": 3, "padding": 1})}))
         has_stem = stem not in (None, nn.Identity)
         stem_width = encoder_width[0] if has_stem else in_channels
 

@@ -1098,6 +1098,37 @@ int fz_inorm_fwd(const void* x, const float* weight, const float* bias, void* y,
 int fz_inorm_bwd(const void* x, const void* gy, const float* weight, const double* stats, void* gx, float* gweight,
                  float* gbias, int64_t P, int C, int64_t V, int act_dtype, void* workspace, fz_stream_t stream);
 
+/* ---- group norm of channels-first activations with a fused activation (csrc/gnorm.hip, csrc/gnorm_core.h; semantics:
+ * factorizer_amd/group_norm.py) ----
+ * The default norm + activation of the CNN blocks (factorizer_amd/cnn.py: nn.GroupNorm(8, C), nn.LeakyReLU).  x, y, gy, gx:
+ * (B, C, *S) contiguous of act_dtype, element-aligned (any storage offset, any V); with G groups a group is cg = C / G adjacent
+ * planes of V elements, one span of n = cg V elements.  weight, bias (C) fp32 or NULL (1 and 0); stats (B G, 2) float64 =
+ * (mean, 1 / sqrt(var + eps)) per group, written by the forward and read by the backward.  All arithmetic is float64, one
+ * rounding per stored element, sums about the group's first element as for the instance norm above:
+ *   z = (x − mean) rstd γ_c + β_c;  y = act(z), act: 0 none, 1 ReLU, 2 LeakyReLU(negative_slope) (FZ_GNORM_ACT_*);
+ *   g' = g (z > 0 ? 1 : slope) (slope 0 for ReLU, no gate for none; closed at z == 0);  per (b, c): s1 = Σ_v g', s2 = Σ_v g' x̂;
+ *   gbias_c = Σ_b s1, gweight_c = Σ_b s2 in batch-index order (either NULL, or its parameter must be given);
+ *   A = Σ_{c in group} γ_c s1 / n, Bq = Σ γ_c s2 / n;  gx = (g' γ_c − A − x̂ Bq) rstd.
+ * No atomics: every sum has a fixed order that depends on (cg, V) and on which parameters are present alone, so results repeat
+ * bit for bit and a group's result depends neither on the rest of the batch nor on its address.  Spans n <=
+ * fz_gnorm_one_pass_max() take one launch each way; larger ones two (fz_gnorm_chunks(cg, V) workgroups per group in the forward
+ * and in the backward's apply launch); gweight / gbias add one: fz_gnorm_launches(cg, V, backward, affine).  workspace:
+ * fz_gnorm_workspace_bytes(B, C, G, V) bytes, 8-byte aligned, scratch of one call (-1: out of range).  B < 1, V < 1, a null
+ * pointer: FZ_E_ARG; act_dtype outside FZ_STORE_*, an unknown activation: FZ_E_UNSUPPORTED; C no multiple of G, n >= 2^31, 2^24
+ * or more workgroups: FZ_E_SHAPE — all before anything touches the device. */
+#define FZ_GNORM_ACT_NONE 0
+#define FZ_GNORM_ACT_RELU 1
+#define FZ_GNORM_ACT_LEAKY_RELU 2
+int fz_gnorm_one_pass_max(void);
+int fz_gnorm_chunks(int cg, int64_t V);
+int64_t fz_gnorm_workspace_bytes(int64_t B, int C, int G, int64_t V);
+int fz_gnorm_launches(int cg, int64_t V, int backward, int affine);
+int fz_gnorm_fwd(const void* x, const float* weight, const float* bias, void* y, double* stats, int64_t B, int C, int G,
+                 int64_t V, double eps, int act, double negative_slope, int act_dtype, void* workspace, fz_stream_t stream);
+int fz_gnorm_bwd(const void* x, const void* gy, const float* weight, const float* bias, const double* stats, void* gx,
+                 float* gweight, float* gbias, int64_t B, int C, int G, int64_t V, int act, double negative_slope,
+                 int act_dtype, void* workspace, fz_stream_t stream);
+
 /* ---- AdamW over one flat buffer (torch.optim.AdamW of the training recipe,
  * model_zoo/factorizer_brats23/configs/train.yaml:72-76).  step >= 1 is the 1-based update count;
  * grad_scale multiplies the gradient first (1/world after a summed all-reduce). */

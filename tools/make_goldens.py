@@ -419,8 +419,55 @@ def g11():
                          f"{name}:y": y, f"{name}:gy": gy, f"{name}:gx": gx})
     npz("g11_solvers", **arrs)
 
+# ---- G12: the CNN blocks and the default UNet (layers/conv.py:12-283, unet.py:177-276) --------------------------------------
+G12_BLOCKS = {  # name: (class, in, out, kwargs); input (2, in, 4, 4, 8)
+    "double": ("DoubleConv", 8, 16, {}), "basic": ("BasicBlock", 8, 16, {}), "preact": ("PreActivationBlock", 8, 16, {}),
+    "sep": ("SepConv", 8, 16, {}), "basic_s2": ("BasicBlock", 8, 16, {"stride": 2}),
+    "preact_s2": ("PreActivationBlock", 8, 16, {"stride": 2}),
+}
+G12_UNETS = {"unet3d": (3, (1, 2, 16, 16, 16)), "unet2d": (2, (1, 2, 32, 32))}
 
-RECIPES = {"g1": g1, "g2_g4": g2_g4, "g5": g5, "g6": g6, "g7": g7, "g8": g8, "g9": g9, "g10": g10, "g11": g11}
+
+def g12():
+    """The four CNN blocks at (8 -> 16, 4x4x8), a stride-2 BasicBlock / PreActivationBlock, and the default (DoubleConv) UNet with
+    a k3 stem, encoder_width (16, 32, 64), strides (1, 2, 2), two decoder stages, in 3-D (16^3) and 2-D (32^2): state_dict keys
+    in order, x, y, dL/dy, dL/dx.  The blocks carry their initial parameters and parameter gradients in full; the UNets, whose
+    parameters alone would exceed the size limit of a fixture, carry a float64 digest of each: sum, sum of absolute values and three projections on fixed random vectors."""
+    from factorizer.layers import conv as C
+    arrs = {}
+
+    def run(name, m, shape, seed, full):
+        g = torch.Generator().manual_seed(seed)
+        x = torch.randn(*shape, generator=g).requires_grad_(True)
+        y = m(x)
+        gy = torch.randn(y.shape, generator=g)
+        names = [k for k, _ in m.named_parameters()]
+        grads = torch.autograd.grad(y, [x] + [p for _, p in m.named_parameters()], gy)
+        arrs.update({f"{name}:keys": np.array(list(m.state_dict())), f"{name}:x": x, f"{name}:y": y, f"{name}:gy": gy,
+                     f"{name}:gx": grads[0]})
+
+        def dig(t):   # sum, sum of absolute values, and three fixed random projections (a permutation or sign error moves them)
+            t = t.detach().double().reshape(-1)
+            r = torch.randn(3, t.numel(), dtype=torch.float64, generator=torch.Generator().manual_seed(t.numel()))
+            return np.array([t.sum().item(), t.abs().sum().item(), *(r @ t).tolist()])
+
+        for k, p, gp in zip(names, m.parameters(), grads[1:]):
+            arrs[f"{name}:p:{k}"] = p if full else dig(p)
+            arrs[f"{name}:g:{k}"] = gp if full else dig(gp)
+
+    for i, (name, (cls, cin, cout, kw)) in enumerate(G12_BLOCKS.items()):
+        torch.manual_seed(1200 + i)
+        run(name, getattr(C, cls)(cin, cout, **kw), (2, cin, 4, 4, 8), 1250 + i, True)
+    for i, (name, (nd, shape)) in enumerate(G12_UNETS.items()):
+        torch.manual_seed(1280 + i)
+        conv = getattr(nn, f"Conv{nd}d")
+        m = ft.UNet(shape[1], 3, spatial_dims=nd, encoder_depth=(1, 1, 1), encoder_width=(16, 32, 64), strides=(1, 2, 2),
+                    decoder_depth=(1, 1), stem=(conv, {"kernel_size": 3, "padding": 1}))
+        run(name, m, shape, 1290 + i, False)
+    npz("g12_cnn", **arrs)
+
+
+RECIPES = {"g1": g1, "g2_g4": g2_g4, "g5": g5, "g6": g6, "g7": g7, "g8": g8, "g9": g9, "g10": g10, "g11": g11, "g12": g12}
 
 if __name__ == "__main__":
     # `python tools/make_goldens.py g11` regenerates one file; no argument: all of them
